@@ -12,11 +12,26 @@ reduction).
 --config c4: the C4 shard instead (configs[3]): 32 GiB at 1 MiB chunks per rank,
 rank r = shard r of the 256 GiB file.
 
-Every rank checks its own digests against the committed golden for its shard
-(tests/golden/c2_ranks.json, c4.json) and the pass flags are gathered into the
-line, so a multi-GPU run validates itself.
+A plain run does only what the headline figure needs: it sets up, warms up,
+times --steps launches and prints the line (metric, value, ms_per_step, the
+workload and the HIP-event roofline arithmetic of the timed launches).
 
-Launch:  python bench.py [--gpus N --steps K --warmup W] [--config c2|c4]
+--dump-outputs DIR: after the timed steps, what the last launch wrote -- the
+(chunks, 20) digest bytes a caller of the path receives -- goes to
+DIR/digests.npy as float32 (DIR/digests_rank<r>.npy per rank at N>1; above
+64 MB a fixed, seeded sample of the rows, their indices in the matching
+*_rows.npy).  The stream is seeded, so the same arguments give the same inputs
+in every run and two builds can be compared digest for digest.
+
+--full: everything else, described below -- the golden check, the recorded
+HBM traffic of the kernel, the host-memory legs, the other configurations and
+the CPU baseline.  The --no-* options drop single legs of a --full run.
+
+With --full every rank checks its own digests against the committed golden for
+its shard (tests/golden/c2_ranks.json, c4.json) and the pass flags are gathered
+into the line, so a multi-GPU run validates itself.
+
+Launch:  python bench.py [--gpus N --steps K --warmup W] [--config c2|c4] [--full] [--dump-outputs DIR]
    N>1, either way:
      python bench.py --gpus N ...              (bench.py starts the N rank processes itself)
      python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
@@ -28,14 +43,14 @@ LBF_BENCH_FORM_GROUP=1 at --gpus 1: rank 0 forms a one-rank process group
 (RCCL unless LBF_BENCH_BACKEND says otherwise) and takes the N>1 route below,
 so every collective of the N-GPU line runs on a 1-GPU box (tests/test_gpu_nccl.py).
 
-N>1 also measures, after the timed region:
+--full at N>1 also measures, after the timed region:
   * e2e: every rank hashes (the first 4 GiB of) its shard from host memory at
     the same moment, pageable and then registered, through its own NUMA-local
     lbf_ctx -- the copy-inclusive rate of north_star at N ranks;
   * e2e_inprocess: rank 0 alone, after the others have finished, hashes one
     registered N x 4 GiB host buffer through ONE lbf_ctx over every visible
     device (Encoder::EncodeFile's shape on an N-GPU node).
-At every N rank 0 then times cpu_baseline (the reference encoder's hash on the
+With --full, at every N rank 0 then times cpu_baseline (the reference encoder's hash on the
 host's usable cores, same stream) once the GPU legs are over.
 """
 import math
@@ -95,6 +110,11 @@ def parse():
     ap.add_argument("--chunk-size", type=int, default=0, help="override the config's chunk size")
     ap.add_argument("--file-gib", type=float, default=0.0, help="override the config's bytes per GPU per step")
     ap.add_argument("--variant", type=int, default=0, help="kernel variant (0 = automatic)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the golden check, the recorded-traffic lookup, the "
+                         "host-memory legs (e2e), the other configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the digests of the last timed step to DIR/digests.npy (float32; per rank at N>1)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this process may use (affinity, capped by the cgroup CPU quota)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -706,6 +726,29 @@ def check_golden(gold, digests):
     return 1 if ok else 0
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: the files of one run together stay below this
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(out_dir, digests, rank, world, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: this rank's (chunks, 20) digest bytes of the last timed
+    launch as float32 (every byte value is exact in it), in <out_dir>/digests.npy
+    (digests_rank<r>.npy at N>1).  When the ranks' files together would pass
+    `max_bytes`, each keeps a fixed, seeded sample of its rows in ascending
+    order and their indices go to the matching *_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    name = "digests" if world == 1 else f"digests_rank{rank}"
+    n = digests.shape[0]
+    # per row: 20 float32 values, plus one float64 index when sampling
+    keep = (max_bytes // world - 4096) // (20 * 4 + 8)
+    if n * 20 * 4 + 4096 <= max_bytes // world:
+        np.save(os.path.join(out_dir, name + ".npy"), digests.astype(np.float32))
+        return
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=keep, replace=False))
+    np.save(os.path.join(out_dir, name + ".npy"), digests[rows].astype(np.float32))
+    np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+
+
 def config_entry(name, length, cs, ms, ok, gold, kernel, pmc_path=None):
     """One other_configs record: rate, HBM fraction and, through the same rule
     as the main line (traffic_from_profiles), the PMC traffic recorded for
@@ -861,11 +904,18 @@ def main():
     launch_s = ev_max / 1e3 / args.steps
     achieved_gbs = file_bytes / launch_s / 1e9
 
-    digests = dig.download(n_chunks * 20).reshape(n_chunks, 20)
-    # every rank checks its own shard against the committed golden
-    gold, gold_path = golden_for_rank(args, rank, file_bytes)
-    per_rank = gather_ints(check_golden(gold, digests), world)
+    full = args.full
+    do_e2e = full and not args.no_e2e
+    # what the last timed launch wrote; a plain run without --dump-outputs leaves it in HBM
+    digests = dig.download(n_chunks * 20).reshape(n_chunks, 20) if full or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, digests, rank, world)
     per_rank_dev = gather_ints(dev, world)
+    gold = gold_path = per_rank = None
+    if full:
+        # every rank checks its own shard against the committed golden
+        gold, gold_path = golden_for_rank(args, rank, file_bytes)
+        per_rank = gather_ints(check_golden(gold, digests), world)
 
     # N>1: the copy-inclusive rate with every rank pulling from host memory at once
     e2e_multi = None
@@ -875,10 +925,10 @@ def main():
         # the host slice, then free the shard's HBM before the host-memory legs:
         # with ranks sharing a GPU (rehearsals: 8 x 32 GiB of C4 on one card)
         # their contexts' device slots would not fit beside it
-        host = buf.download(slice_bytes) if not args.no_e2e else None
+        host = buf.download(slice_bytes) if do_e2e else None
         buf.free()
         buf = None
-    if multi and not args.no_e2e and n_slice:
+    if multi and do_e2e and n_slice:
         r = e2e_leg(host, cs, dev, world)
         del host
         ok = int(np.array_equal(r["digests"], digests[:n_slice]) and r["registered_equal"] and r["autopin_equal"])
@@ -912,15 +962,18 @@ def main():
         e2e_multi["failed_per_rank"] = gather_ints(r["error"] is not None, world)
         if r["error"]:
             e2e_multi["error_rank0"] = r["error"]
-    slice_hashes = gather_ints(slice_hash(digests[:n_slice]), world)
+    slice_hashes = gather_ints(slice_hash(digests[:n_slice]), world) if full else None
     gpu0_numa = None
     shard_starts = [shard_range(world * n_chunks, q, world)[0] * cs for q in range(world)]
 
     variant = H.load().lbf_kernel_for(n_chunks)
     floor_ms = compute_floor_ms(variant, cs, n_chunks)
     kernel = KERNELS.get(variant, str(variant))
-    code_sym, code_sha = kernel_code_digest(kernel)
-    traffic, traffic_src, traffic_null = traffic_from_profiles(file_bytes, cs, kernel, code_sha)
+    code_sym = code_sha = traffic = traffic_src = None
+    traffic_null = "the recorded-traffic lookup runs with --full"
+    if full:
+        code_sym, code_sha = kernel_code_digest(kernel)
+        traffic, traffic_src, traffic_null = traffic_from_profiles(file_bytes, cs, kernel, code_sha)
     out = None
     if rank == 0:
         c2 = (file_bytes, cs) == (4 * GIB, 262144)
@@ -986,12 +1039,7 @@ def main():
                 "frac": round(floor_ms / (launch_s * 1e3), 4),
                 "clock_ghz": CLOCK_HZ / 1e9,
             },
-            "digest_check": hashlib.sha1(digests.tobytes()).hexdigest(),
-            "parity": {
-                "golden": gold_path,
-                "per_rank": per_rank,  # 1 match, 0 mismatch, -1 no golden for that shard
-                "all_ranks_match_golden": all(x == 1 for x in per_rank),
-            },
+            "full": full,
             "ranks": {
                 "launcher": os.environ.get("LBF_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "none"),
                 "process_group": backend_name() if multi else None,
@@ -1004,10 +1052,20 @@ def main():
         if world > ndev:
             out["ranks"]["note"] = (f"{world} ranks share {ndev} GPU(s): a rehearsal of the N-rank flow; their "
                                     "launches queue on the shared device, so value is not an N-GPU rate")
+        if full:
+            out["digest_check"] = hashlib.sha1(digests.tobytes()).hexdigest()
+            out["parity"] = {
+                "golden": gold_path,
+                "per_rank": per_rank,  # 1 match, 0 mismatch, -1 no golden for that shard
+                "all_ranks_match_golden": all(x == 1 for x in per_rank),
+            }
+            out["first_chunk_b64"] = b64_27(bytes(digests[0]))
+        if args.dump_outputs:
+            out["dump_outputs"] = args.dump_outputs
         if e2e_multi is not None:
             out["e2e"] = e2e_multi
         if not multi:
-            if not args.no_e2e:
+            if do_e2e:
                 # the whole file, copied back from HBM into pageable host memory
                 host_file = buf.download(file_bytes)
                 r = e2e_leg(host_file, cs, dev, 1)
@@ -1030,12 +1088,11 @@ def main():
                 if r["error"]:
                     out["e2e_error"] = r["error"]
                 gpu0_numa = r["placement"]["numa_node"]
-        out["first_chunk_b64"] = b64_27(bytes(digests[0]))
     if multi:
         import torch.distributed as dist
         barrier(world)  # every rank's e2e leg has ended before rank 0 goes on alone
         dist.destroy_process_group()
-    if rank == 0 and multi and not args.no_e2e and not args.no_inproc and n_slice:
+    if rank == 0 and multi and do_e2e and not args.no_inproc and n_slice:
         gen = None
         try:
             gen = DeviceBuffer(slice_bytes)
@@ -1048,9 +1105,9 @@ def main():
     if buf is not None:
         buf.free()
     dig.free()
-    if rank == 0 and not multi and not args.no_other_configs and args.config == "c2":
+    if rank == 0 and full and not multi and not args.no_other_configs and args.config == "c2":
         out["other_configs"] = other_configs()
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and full and not args.no_cpu_baseline:
         # at every N, rank 0 alone once the GPU legs are over (the other ranks
         # have left the group), on the same stream as its shard
         sample = min(n_chunks, max(1, GIB // cs))

@@ -116,7 +116,9 @@ def test_gloo_connect_notice_stays_off_stdout(tmp_path):
 N_LINE_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                "vs_baseline", "dtype", "data", "config", "roofline", "compute_floor", "cpu_baseline", "parity",
                "ranks", "e2e", "e2e_inprocess", "digest_check", "first_chunk_b64"}
-FAKE_ARGV = ["--steps", "2", "--warmup", "1", "--file-gib", "0.0625", "--cpu-min-s", "0.3"]
+PLAIN_ARGV = ["--steps", "2", "--warmup", "1", "--file-gib", "0.0625"]
+# everything beyond the timed steps (parity, host-memory legs, cpu_baseline) is behind --full
+FAKE_ARGV = PLAIN_ARGV + ["--full", "--cpu-min-s", "0.3"]
 
 
 def _check_line(out, n):
@@ -211,3 +213,67 @@ def test_failing_cpu_baseline_still_prints_the_line():
     out = json.loads([x for x in p.stdout.splitlines() if x.strip()][-1])
     assert out["value"] > 0 and out["roofline"]["achieved"] > 0
     assert out["cpu_baseline"]["value"] is None and "injected" in out["cpu_baseline"]["error"]
+
+
+# What only a --full run measures or checks: absent from a plain line.
+FULL_ONLY_KEYS = {"cpu_baseline", "e2e", "e2e_inprocess", "e2e_host_to_host_gibs", "e2e_registered", "e2e_autopin",
+                  "other_configs", "parity", "digest_check", "first_chunk_b64"}
+
+
+def _plain_run(extra, timeout=300):
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LBF_BENCH_FORM_GROUP")}
+    p = subprocess.run([sys.executable, FAKE, "--gpus", "1"] + PLAIN_ARGV + list(extra), env=env, capture_output=True,
+                       text=True, timeout=timeout, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [x for x in p.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_the_steps_and_nothing_else(tmp_path, oracle):
+    """Without --full the line holds the headline figure of the --steps timed
+    launches and none of the legs that follow them; --dump-outputs writes the
+    last launch's digests as float32, the same bytes in every run."""
+    import hashlib
+
+    import numpy as np
+    outs = [_plain_run(["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    out = outs[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "config"} <= set(out)
+    assert not FULL_ONLY_KEYS & set(out), FULL_ONLY_KEYS & set(out)
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["full"] is False
+    assert out["unit"] == "GiB/s" and out["higher_is_better"] is True and out["dtype"] == "u32"
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["roofline"]["traffic"] is None
+    # value is the bytes of the timed steps over their wall time, ms_per_step that time per step
+    assert abs(out["value"] * out["ms_per_step"] / 1e3 - 0.0625) < 1e-3 * 0.0625 + 1e-4
+    a, b = (np.load(tmp_path / d / "digests.npy") for d in ("a", "b"))
+    cs, n = 262144, 256
+    assert a.dtype == np.float32 and a.shape == (n, 20) and np.array_equal(a, b)
+    data = oracle.synth(0x5EED, 0, n * cs)
+    want = np.array([list(hashlib.sha1(data[i * cs:(i + 1) * cs].tobytes()).digest()) for i in range(n)])
+    assert np.array_equal(a, want.astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "a")) == ["digests.npy"]
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path):
+    """Above the size limit each rank keeps a fixed, seeded sample of its rows:
+    the same rows every time, in ascending order, and the files stay below the
+    limit together."""
+    import numpy as np
+    d = (np.arange(5000 * 20) % 251).astype(np.uint8).reshape(5000, 20)
+    limit = 64 << 10
+    for sub in ("a", "b"):
+        for rank in range(2):
+            bench.dump_outputs(str(tmp_path / sub), d, rank, 2, max_bytes=limit)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["digests_rank0.npy", "digests_rank0_rows.npy", "digests_rank1.npy", "digests_rank1_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= limit
+    rows = np.load(tmp_path / "a" / "digests_rank0_rows.npy")
+    got = np.load(tmp_path / "a" / "digests_rank0.npy")
+    assert got.dtype == np.float32 and rows.dtype == np.float64 and len(rows) > 300
+    assert np.all(np.diff(rows) > 0) and np.array_equal(got, d[rows.astype(np.int64)].astype(np.float32))
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    # an output that fits is written whole, with no row file
+    bench.dump_outputs(str(tmp_path / "c"), d[:100], 0, 1, max_bytes=limit)
+    assert os.listdir(tmp_path / "c") == ["digests.npy"] and np.load(tmp_path / "c" / "digests.npy").shape == (100, 20)

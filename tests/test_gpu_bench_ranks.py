@@ -1,5 +1,5 @@
 """bench.py's multi-rank flow on the GPU box, launched the way a driver runs it:
-`python bench.py --gpus 2` with no launcher (bench.py starts its own ranks).
+`python bench.py --gpus 2 --full` with no launcher (bench.py starts its own ranks).
 With one GPU the two ranks share it under gloo (a rehearsal); what is checked
 is the flow: two ranks, each rank's device-resident digests equal the oracle
 on its shard, and the N-rank host-memory legs (e2e, e2e_inprocess) report
@@ -22,7 +22,7 @@ def test_bench_self_launched_two_ranks(oracle):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env["LBF_BENCH_BACKEND"] = "gloo"
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-            "--file-gib", "0.25", "--cpu-min-s", "0.5"]
+            "--file-gib", "0.25", "--cpu-min-s", "0.5", "--full"]
     p = subprocess.run(args, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]

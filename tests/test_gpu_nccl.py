@@ -66,7 +66,7 @@ def test_bench_one_rank_rccl_group_takes_the_n_rank_route(oracle):
     env.update(RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(bench._free_port()),
                LBF_BENCH_FORM_GROUP="1")
     args = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-            "--file-gib", "0.25", "--cpu-min-s", "0.5"]
+            "--file-gib", "0.25", "--cpu-min-s", "0.5", "--full"]
     p = subprocess.run(args, env=env, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]

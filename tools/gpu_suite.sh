@@ -20,6 +20,6 @@ step() {  # step <name> <seconds> <cmd...>
 }
 step pytest_gpu 700 python -u -m pytest tests -m gpu -v -rP --durations=15 --timeout 300 --timeout-method thread -p no:cacheprovider ${only:+-k "$only"} &&
 step latency 120 bitflood_amd/lib/lbf_latency --reps 200 &&
-step bench_c2 300 python bench.py --steps 20 --warmup 5 &&
+step bench_c2 300 python bench.py --steps 20 --warmup 5 --full &&
 step bench_2rank_gloo 300 env LBF_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2
+  --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --full
