@@ -280,6 +280,7 @@ def test_uniform_partial_last_chunk(variant, oracle):
     n_bytes = (5 << 20) + 12345
     buf = DeviceBuffer(n_bytes)
     dig = DeviceBuffer(21 * 20)
+    ver = DeviceBuffer(21)
     try:
         buf.fill_synthetic(77)
         n = (n_bytes + 262143) // 262144
@@ -292,9 +293,23 @@ def test_uniform_partial_last_chunk(variant, oracle):
         H.uniform_launch(buf, n_bytes, 262144, 7, n - 7, dig)
         H.synchronize()
         assert np.array_equal(dig.download((n - 7) * 20).reshape(n - 7, 20), want[7:])
+        # verify mode over the whole region, three expected digests off by a bit
+        flipped = [0, 9, n - 1]
+        exp = want.copy()
+        exp[0, 0] ^= 0x01
+        exp[9, 7] ^= 0x10
+        exp[n - 1, 19] ^= 0x80
+        dig.upload(exp)
+        ver.upload(np.full(n, 0xA5, dtype=np.uint8))
+        H.uniform_launch(buf, n_bytes, 262144, 0, n, None, expected=dig, verdicts=ver)
+        H.synchronize()
+        v = ver.download(n)
+        assert np.flatnonzero(v == 0).tolist() == flipped
+        assert (np.delete(v, flipped) == 1).all()
     finally:
         buf.free()
         dig.free()
+        ver.free()
 
 
 def test_c2_full_size_device_resident(variant, golden, oracle):
