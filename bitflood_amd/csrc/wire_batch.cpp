@@ -1,0 +1,325 @@
+// wire_batch.cpp -- the two batch calls of the wire (base64) form: chunks to
+// send are verified and encoded, received chunks are decoded and verified, on
+// the device, synchronously on worker 0's first stream.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include <algorithm>
+
+#include "lbf_host.hpp"
+
+using namespace lbf;
+
+namespace {
+
+// The device memory of the two base64 entry points: one allocation on worker
+// 0's device (current when this runs), grown on demand; the caller holds ctx->mu.
+int b64_scratch(lbf_ctx* ctx, uint64_t need, const char* who) {
+  if (need <= ctx->b64_cap) return LBF_OK;
+  if (ctx->b64_dev) (void)hipFree(ctx->b64_dev);
+  ctx->b64_dev = nullptr;
+  ctx->b64_cap = 0;
+  const uint64_t want = std::max<uint64_t>(need, 64ull << 20);
+  if (hipMalloc(reinterpret_cast<void**>(&ctx->b64_dev), want) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LBF_ERR_NOMEM, std::string(who) + ": device allocation of " + std::to_string(want) + " bytes");
+  }
+  ctx->b64_cap = want;
+  return LBF_OK;
+}
+
+// Every exit of a base64 entry point after its first async copy waits for the
+// stream, so no copy is still reading a local staging vector or the caller's
+// (possibly pinned) buffers, or writing into them, once the call has returned
+// (ADVICE r04).  Declared after the host vectors the copies use, so it runs
+// before they are destroyed.
+struct SyncOnExit {
+  hipStream_t st;
+  ~SyncOnExit() {
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+  }
+};
+
+// The runs of caller slots a D2H writes (stage_plan.hpp, slot_runs).
+int checked_slot_runs(const uint64_t* off, const uint64_t* len, uint64_t n, const char* who,
+                      std::vector<SlotRun>& runs) {
+  const uint64_t bad = slot_runs(off, len, n, runs);
+  if (bad == kNoSlot) return LBF_OK;
+  return fail(LBF_ERR_INVALID, std::string(who) + ": slot " + std::to_string(bad) + " overlaps another slot");
+}
+
+uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
+// The wire kernels keep text and byte positions inside a chunk, and their
+// tile counts, in 32 bits (kern_b64.hpp): (len + tile - 1) / tile and
+// tile * tile_text must not wrap, so chunks are bounded well below 2^32.  The
+// reference's chunks are 64 KiB to a few MiB (Encoder.cpp:17-102); 1 GiB of
+// bytes encodes to 1.43 GB of text.  ADVICE r05: past 2^32 the positions
+// wrapped and tiles were never launched.
+constexpr uint64_t kB64MaxChunk = 1ull << 30, kB64MaxText = 3ull << 29;
+
+}  // namespace
+
+extern "C" uint64_t lbf_b64_put_length(uint64_t size) { return 4 * (size / 3) + (size % 3 ? 4 : 0) + size / 3 / 18; }
+
+// Chunks to send: verify on the device (ChunkMethods.cpp:116-123), then encode
+// each as the base64 text of its SendChunk frame (XmlRpcValue.cpp:439-452,
+// kern_b64.hpp), from the same
+// device copy.  Synchronous on worker 0's first stream: one H2D of the bytes'
+// span and one of the tables, two launches, one D2H of the verdicts and one of
+// the text span.
+extern "C" int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len,
+                                           const uint64_t* offsets, const uint32_t* sizes, uint64_t n,
+                                           const uint8_t* expected, uint8_t* verdicts, char* text, uint64_t text_len,
+                                           const uint64_t* text_offsets) {
+  if (!ctx) return fail(LBF_ERR_INVALID, "null context");
+  if (n == 0) return LBF_OK;
+  if (!data || !offsets || !sizes || !expected || !verdicts || !text || !text_offsets)
+    return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: null argument");
+  if (n > 0x7FFFFFFFull) return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: n too large");
+  uint64_t dlo = UINT64_MAX, dhi = 0, tlo = UINT64_MAX, thi = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (sizes[i] > kB64MaxChunk)
+      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: chunk " + std::to_string(i) +
+                                       " larger than the wire encode takes (1 GiB)");
+    if (offsets[i] > data_len || sizes[i] > data_len - offsets[i])
+      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: chunk " + std::to_string(i) + " outside the buffer");
+    const uint64_t tl = lbf_b64_put_length(sizes[i]);
+    if (text_offsets[i] > text_len || tl > text_len - text_offsets[i])
+      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: text slot " + std::to_string(i) + " outside the buffer");
+    dlo = std::min(dlo, offsets[i]);
+    dhi = std::max(dhi, offsets[i] + sizes[i]);
+    tlo = std::min(tlo, text_offsets[i]);
+    thi = std::max(thi, text_offsets[i] + tl);
+  }
+  uint32_t max_size = 0;
+  for (uint64_t i = 0; i < n; ++i) max_size = std::max(max_size, sizes[i]);
+  std::vector<uint64_t> tlens(n);
+  for (uint64_t i = 0; i < n; ++i) tlens[i] = lbf_b64_put_length(sizes[i]);
+  std::vector<SlotRun> runs;  // the text slots the D2H writes, and nothing between them
+  if (int rc = checked_slot_runs(text_offsets, tlens.data(), n, "lbf_verify_encode_b64_batch", runs)) return rc;
+  dlo &= ~15ull;  // device offsets keep the host offsets' alignment mod 16
+  tlo &= ~15ull;
+  return guarded([&] {
+    std::vector<uint8_t> in(n * (8 + 8 + 4 + 20));
+    uint64_t* doff = reinterpret_cast<uint64_t*>(in.data());
+    uint64_t* toff = doff + n;
+    uint32_t* sz = reinterpret_cast<uint32_t*>(toff + n);
+    for (uint64_t i = 0; i < n; ++i) {
+      doff[i] = offsets[i] - dlo;
+      toff[i] = text_offsets[i] - tlo;
+      sz[i] = sizes[i];
+    }
+    memcpy(sz + n, expected, 20 * n);
+    // device layout: bytes | text | inputs (offsets, text offsets, sizes, expected) | verdicts
+    const uint64_t data_b = up(dhi - dlo + 16, 256), text_b = up(thi - tlo + 16, 256), in_b = up(in.size(), 256);
+    const uint64_t need = data_b + text_b + in_b + up(n, 256);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    KeepCurrentDevice keep;
+    Worker& w = ctx->workers[0];
+    LBF_HIP_TRY(hipSetDevice(w.device));
+    if (int rc = b64_scratch(ctx, need, "lbf_verify_encode_b64_batch")) return rc;
+    uint8_t* d_data = ctx->b64_dev;
+    uint8_t* d_text = d_data + data_b;
+    uint8_t* d_in = d_text + text_b;
+    uint8_t* d_ver = d_in + in_b;
+    hipStream_t st = w.dev[0].stream;
+    SyncOnExit sync{st};
+    if (dhi > dlo) LBF_HIP_TRY(hipMemcpyAsync(d_data, data + dlo, dhi - dlo, hipMemcpyHostToDevice, st));
+    LBF_HIP_TRY(hipMemcpyAsync(d_in, in.data(), in.size(), hipMemcpyHostToDevice, st));
+    const uint64_t* d_doff = reinterpret_cast<const uint64_t*>(d_in);
+    const uint64_t* d_toff = d_doff + n;
+    const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_toff + n);
+    const uint8_t* d_exp = reinterpret_cast<const uint8_t*>(d_sz + n);
+    if (int rc = lbf_sha1_launch(d_data, d_doff, d_sz, n, nullptr, d_exp, d_ver, st)) return rc;
+    if (int rc = lbf::launch_b64_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st)) return rc;
+    LBF_HIP_TRY(hipMemcpyAsync(verdicts, d_ver, n, hipMemcpyDeviceToHost, st));
+    for (const SlotRun& r : runs)
+      LBF_HIP_TRY(hipMemcpyAsync(text + r.lo, d_text + (r.lo - tlo), r.hi - r.lo, hipMemcpyDeviceToHost, st));
+    LBF_HIP_TRY(hipStreamSynchronize(st));
+    return (int)LBF_OK;
+  });
+}
+
+namespace {
+
+// One lbf_b64_verify_batch call: the caller's arguments, and what the checks
+// derive from them.
+struct B64Verify {
+  const char* text;
+  const uint64_t* text_offsets;
+  const uint32_t* text_lens;
+  uint64_t n;
+  const uint32_t* expected_sizes;
+  const uint8_t* expected;
+  uint8_t* out;
+  const uint64_t* out_offsets;
+  uint32_t* out_sizes;
+  uint8_t* verdicts;
+  uint64_t tlo = UINT64_MAX, thi = 0, olo = UINT64_MAX, ohi = 0;  // the spans of the text and of the output slots
+  uint32_t max_tlen = 0, max_cap = 0;
+  std::vector<SlotRun> runs;  // the output slots the D2H writes, and nothing between them
+  // bytes per chunk of the inputs (offsets, lengths, caps, expected) and of the results (sizes, over,
+  // verdicts, redo flags); kIn * n keeps 4-byte alignment
+  static constexpr uint64_t kIn = 8 * 3 + 4 * 2 + 20, kRes = 4 + 1 + 1 + 1;
+};
+
+int b64_verify_check(B64Verify& v, uint64_t text_len, uint64_t out_len) {
+  const uint64_t n = v.n;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (v.text_lens[i] > kB64MaxText || v.expected_sizes[i] > kB64MaxChunk)
+      return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: chunk " + std::to_string(i) +
+                                       " larger than the wire decode takes (1 GiB of bytes, 1.5 GiB of text)");
+    if (v.text_offsets[i] > text_len || v.text_lens[i] > text_len - v.text_offsets[i])
+      return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: text range " + std::to_string(i) + " outside the buffer");
+    v.tlo = std::min(v.tlo, v.text_offsets[i]);
+    v.thi = std::max(v.thi, v.text_offsets[i] + v.text_lens[i]);
+    if (v.out) {
+      if (v.out_offsets[i] > out_len || v.expected_sizes[i] > out_len - v.out_offsets[i])
+        return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: output slot " + std::to_string(i) + " outside the buffer");
+      v.olo = std::min(v.olo, v.out_offsets[i]);
+      v.ohi = std::max(v.ohi, v.out_offsets[i] + v.expected_sizes[i]);
+    }
+  }
+  // device offsets keep the host offsets' alignment mod 16; the D2H writes the
+  // output slots and nothing between them
+  if (v.out) {
+    std::vector<uint64_t> olens(v.expected_sizes, v.expected_sizes + n);
+    if (int rc = checked_slot_runs(v.out_offsets, olens.data(), n, "lbf_b64_verify_batch", v.runs)) return rc;
+  }
+  for (uint64_t i = 0; i < n; ++i) {
+    v.max_tlen = std::max(v.max_tlen, v.text_lens[i]);
+    v.max_cap = std::max(v.max_cap, v.expected_sizes[i]);
+  }
+  v.tlo &= ~15ull;
+  if (v.out) v.olo &= ~15ull;
+  return LBF_OK;
+}
+
+// The upload of one call: the inputs and, right behind them, the zeroed
+// results, so one H2D carries both and one D2H brings the results back.
+// Returns the bytes of sextet scratch and of decoded output the device needs.
+std::vector<uint8_t> b64_verify_tables(const B64Verify& v, uint64_t& sext, uint64_t& outb) {
+  const uint64_t n = v.n;
+  std::vector<uint64_t> toff(n), soff(n), ooff(n);
+  std::vector<uint32_t> tlen(n), cap(n);
+  sext = 0, outb = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    toff[i] = v.text_offsets[i] - v.tlo;
+    soff[i] = sext;
+    sext += up(v.text_lens[i], 16);
+    tlen[i] = v.text_lens[i];
+    cap[i] = v.expected_sizes[i];
+    if (v.out) {
+      ooff[i] = v.out_offsets[i] - v.olo;
+    } else {
+      ooff[i] = outb;
+      outb += up(v.expected_sizes[i], 16);
+    }
+  }
+  if (v.out) outb = v.ohi - v.olo;
+  std::vector<uint8_t> in(n * (B64Verify::kIn + B64Verify::kRes), 0);
+  uint8_t* q = in.data();
+  auto put = [&](const void* src, uint64_t bytes) {
+    memcpy(q, src, bytes);
+    q += bytes;
+  };
+  put(toff.data(), 8 * n);
+  put(soff.data(), 8 * n);
+  put(ooff.data(), 8 * n);
+  put(tlen.data(), 4 * n);
+  put(cap.data(), 4 * n);
+  put(v.expected, 20 * n);
+  return in;
+}
+
+// The results of one call (sizes, over, verdicts, redo flags per chunk) as the
+// caller's verdicts and sizes, and the context's decode-path counters.
+void b64_verify_results(lbf_ctx* ctx, const B64Verify& v, const std::vector<uint8_t>& res) {
+  const uint64_t n = v.n;
+  const uint8_t* redo = res.data() + 6 * n;
+  uint64_t general = 0;
+  for (uint64_t i = 0; i < n; ++i) general += redo[i] != 0;
+  ctx->b64_general += general;
+  ctx->b64_one_pass += n - general;
+  const uint32_t* sizes = reinterpret_cast<const uint32_t*>(res.data());
+  const uint8_t* over = res.data() + 4 * n;
+  const uint8_t* ver = over + n;
+  for (uint64_t i = 0; i < n; ++i) {
+    // ChunkMethods.cpp:156: the decoded length must be the chunk's size
+    const bool longer = over[i] != 0;
+    v.verdicts[i] = (ver[i] && !longer && sizes[i] == v.expected_sizes[i]) ? 1 : 0;
+    if (v.out_sizes) v.out_sizes[i] = longer ? v.expected_sizes[i] + 1 : sizes[i];
+  }
+}
+
+int b64_verify_run(lbf_ctx* ctx, const B64Verify& v) {
+  const uint64_t n = v.n, kIn = B64Verify::kIn, kRes = B64Verify::kRes;
+  uint64_t sext = 0, outb = 0;
+  const std::vector<uint8_t> in = b64_verify_tables(v, sext, outb);
+  // device layout: text | sextets | bytes | inputs then, right behind them, the results
+  const uint64_t text_b = up(v.thi - v.tlo, 256), sext_b = up(sext, 256), out_b = up(outb + 16, 256);
+  const uint64_t io_b = up(n * (kIn + kRes), 256);
+  const uint64_t need = text_b + sext_b + out_b + io_b;
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  KeepCurrentDevice keep;
+  Worker& w = ctx->workers[0];
+  LBF_HIP_TRY(hipSetDevice(w.device));
+  if (int rc = b64_scratch(ctx, need, "lbf_b64_verify_batch")) return rc;
+  uint8_t* d_text = ctx->b64_dev;
+  uint8_t* d_sext = d_text + text_b;
+  uint8_t* d_out = d_sext + sext_b;
+  uint8_t* d_in = d_out + out_b;
+  uint8_t* d_res = d_in + kIn * n;
+  hipStream_t st = w.dev[0].stream;
+  std::vector<uint8_t> res(n * kRes);
+  SyncOnExit sync{st};
+  if (v.thi > v.tlo) LBF_HIP_TRY(hipMemcpyAsync(d_text, v.text + v.tlo, v.thi - v.tlo, hipMemcpyHostToDevice, st));
+  LBF_HIP_TRY(hipMemcpyAsync(d_in, in.data(), in.size(), hipMemcpyHostToDevice, st));
+  const uint64_t* d_toff = reinterpret_cast<const uint64_t*>(d_in);
+  const uint64_t* d_soff = d_toff + n;
+  const uint64_t* d_ooff = d_soff + n;
+  const uint32_t* d_tlen = reinterpret_cast<const uint32_t*>(d_ooff + n);
+  const uint32_t* d_cap = d_tlen + n;
+  const uint8_t* d_exp = reinterpret_cast<const uint8_t*>(d_cap + n);
+  uint32_t* d_sizes = reinterpret_cast<uint32_t*>(d_res);
+  uint8_t* d_over = reinterpret_cast<uint8_t*>(d_sizes + n);
+  uint8_t* d_ver = d_over + n;
+  uint8_t* d_redo = d_ver + n;  // uploaded as zeros
+  lbf::B64Launch b{d_text, d_sext, d_toff, d_soff, d_tlen, d_out,   d_ooff, d_cap,
+                   d_sizes, d_over, d_redo, (uint32_t)n, v.max_tlen, v.max_cap};
+  if (int rc = lbf::launch_b64_decode(b, st)) return rc;
+  // the decoded lengths are the chunk sizes the hash kernels read
+  if (int rc = lbf_sha1_launch(d_out, d_ooff, d_sizes, n, nullptr, d_exp, d_ver, st)) return rc;
+  LBF_HIP_TRY(hipMemcpyAsync(res.data(), d_res, res.size(), hipMemcpyDeviceToHost, st));
+  for (const SlotRun& r : v.runs)
+    LBF_HIP_TRY(hipMemcpyAsync(v.out + r.lo, d_out + (r.lo - v.olo), r.hi - r.lo, hipMemcpyDeviceToHost, st));
+  LBF_HIP_TRY(hipStreamSynchronize(st));
+  b64_verify_results(ctx, v, res);
+  return LBF_OK;
+}
+
+}  // namespace
+
+// Received chunks as base64 text: decode on the device (kern_b64.hpp), then
+// the shipped hash kernels verify the decoded bytes in HBM.  Synchronous on
+// worker 0's first stream: one H2D of the text span and one of the tables, two
+// launches, one D2H of the results and one of the decoded span.
+extern "C" int lbf_b64_verify_batch(lbf_ctx* ctx, const char* text, uint64_t text_len,
+                                    const uint64_t* text_offsets, const uint32_t* text_lens, uint64_t n,
+                                    const uint32_t* expected_sizes, const uint8_t* expected, uint8_t* out,
+                                    uint64_t out_len, const uint64_t* out_offsets, uint32_t* out_sizes,
+                                    uint8_t* verdicts) {
+  if (!ctx) return fail(LBF_ERR_INVALID, "null context");
+  if (n == 0) return LBF_OK;
+  if (!text || !text_offsets || !text_lens || !expected_sizes || !expected || !verdicts)
+    return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: null argument");
+  if (out && !out_offsets) return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: out without out_offsets");
+  if (n > 0x7FFFFFFFull) return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: n too large");
+  return guarded([&] {
+    B64Verify v{text, text_offsets, text_lens, n, expected_sizes, expected, out, out_offsets, out_sizes, verdicts};
+    if (int rc = b64_verify_check(v, text_len, out_len)) return rc;
+    return b64_verify_run(ctx, v);
+  });
+}

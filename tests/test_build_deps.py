@@ -18,10 +18,14 @@ def _prereqs(target):
     raise AssertionError(f"{target} not in make's database")
 
 
-def test_every_header_is_a_prerequisite_of_both_objects():
+def test_every_header_is_a_prerequisite_of_every_object():
     headers = {os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hpp"))}
-    assert "kern_b64.hpp" in headers
-    for obj in ("../lib/sha1_kernels.o", "../lib/lbf_capi.o"):
+    assert {"kern_b64.hpp", "stage_plan.hpp"} <= headers
+    objects = sorted(p for p in _prereqs("../lib/liblbfhash.so") if p.endswith(".o"))
+    assert {"../lib/sha1_kernels.o", "../lib/lbf_capi.o", "../lib/staging.o"} <= set(objects)
+    for obj in objects:
         pre = _prereqs(obj)
         assert headers <= pre, (obj, headers - pre)
         assert "../../include/lbf_hash.h" in pre
+        sources = [p for p in pre if p.endswith((".cpp", ".hip"))]
+        assert len(sources) == 1, (obj, sources)

@@ -3,7 +3,7 @@
 The reference's Base64Encode builds its hasher on the stack per call, so any
 number of threads may call it (/root/reference/cpp/src/Encoder.cpp:107-120;
 SURVEY.md §8b).  The drop-in keeps that promise with one context per process
-whose calls serialize on the context (lbf_capi.cpp run_job / run_device_job)
+whose calls serialize on the context (staging.cpp run_job / run_device_job)
 and a thread-local last-error string.  These tests hammer one context from
 several host threads (ctypes drops the GIL for the call, so the calls really
 overlap on the host) with a mix of hash, verify, one-buffer and file batches,

@@ -219,6 +219,46 @@ def test_staging_slot_counts(slots, oracle, monkeypatch):
         h.close()
 
 
+def test_multi_piece_batches_and_short_read_across_pieces(oracle, monkeypatch, tmp_path):
+    """The multi-piece staged route: with 4 MiB device slots and 1 MiB pinned
+    host slots every full batch (63 chunks of 65,549 bytes) travels as four
+    pieces through the host ring, then its header from the slot's own pinned
+    header buffer.  From memory and from a file; a file cut inside the second
+    piece of the second batch leaves exactly the chunks past the cut
+    unverified, and hashing it is an IO error."""
+    with monkeypatch.context() as m:  # read at context creation only
+        m.setenv("LBF_SLOT_MB", "4")
+        m.setenv("LBF_PIN_MB", "1")
+        h = ChunkHasher(device_mask=1)
+    try:
+        data = oracle.synth(83, 0, (12 << 20) + 333)
+        offs, sizes = chunk_table(data.size - 5, 65549)
+        offs = offs + np.uint64(5)
+        assert int(sizes[-1]) != 65549 and int(offs[-1]) + int(sizes[-1]) == data.size
+        covered = data.size - 5
+        want = oracle.sha1_batch(data, offs, sizes)
+        path = tmp_path / "f.bin"
+        path.write_bytes(data.tobytes())
+        for hash_it in (lambda: h.hash_chunks(data, offs, sizes), lambda: h.hash_file(str(path), offs, sizes)):
+            s0 = h.staging_stats()
+            assert np.array_equal(hash_it(), want)
+            s1 = h.staging_stats()
+            assert s1["direct"] == s0["direct"]
+            assert covered <= s1["staged"] - s0["staged"] < covered + 16 * offs.size, (s0, s1)
+        assert h.verify_file(str(path), offs, sizes, want).all()
+        cut = (4 << 20) + (3 << 19) + 7
+        short = tmp_path / "short.bin"
+        short.write_bytes(data[:cut].tobytes())
+        v = h.verify_file(str(short), offs, sizes, want)
+        assert v.tolist() == ((offs + sizes.astype(np.uint64)) <= np.uint64(cut)).tolist()
+        assert v.any() and not v.all()
+        with pytest.raises(Exception, match="could not be read in full"):
+            h.hash_file(str(short), offs, sizes)
+        assert h.staging_stats()["direct"] == 0
+    finally:
+        h.close()
+
+
 def test_device_fill_matches_oracle_stream(oracle):
     buf = DeviceBuffer(1 << 20)
     try:
@@ -432,7 +472,7 @@ def test_more_chunks_than_one_group_holds(hasher, oracle):
 
 def test_unsorted_overlapping_duplicate_table(hasher, oracle):
     """The staging sorts descriptors by offset and packs them as joined runs
-    (lbf_capi.cpp worker_run); results must land at the caller's indices:
+    (stage_plan.hpp, staging.cpp worker_run); results land at the caller's indices:
     a descending table, exact duplicates, chunks nested in others, chunks far
     apart, and empty chunks anywhere, in hash and verify mode."""
     buf = oracle.synth(71, 0, 64 << 20, nthreads=8)

@@ -1,7 +1,7 @@
 """The multi-worker host path of lbf_ctx on one GPU, and its error paths.
 
 On an 8-GPU node every EncodeFile / SetupFilesAndChunks runs through
-run_job's multi-worker branch (bitflood_amd/csrc/lbf_capi.cpp): contiguous
+run_job's multi-worker branch (bitflood_amd/csrc/staging.cpp): contiguous
 index ranges, one host thread, one set of staging slots per worker, the first
 failing worker's status and message returned (the reference's one-thread loop
 it replaces: /root/reference/cpp/src/Encoder.cpp:40-79, Flood.cpp:243-285).

@@ -10,7 +10,7 @@ all in one process and lease, best of 3 after a warm pass:
   reg_pipelined pieces of --piece-mib: a helper thread registers piece k+1 (and
                 unregisters piece k-1) while piece k is hashed straight from
                 pinned memory; registration and hashing timed together
-  autopin       the library's own on-the-fly pinning (lbf_capi.cpp AutoPin; the
+  autopin       the library's own on-the-fly pinning (pinning.cpp AutoPin; the
                 default since round 5): the job's span registered in one piece
   registered    the buffer registered outside the timing (what a caller that
                 reuses its buffer gets: the ceiling of the pinned routes)

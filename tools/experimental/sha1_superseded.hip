@@ -3,7 +3,7 @@
 // nothing here is in bitflood_amd/lib/liblbfhash.so.
 //
 // `make -C tools/experimental` links this translation unit with the shipped
-// objects (bitflood_amd/lib/sha1_kernels.o, lbf_capi.o) into
+// objects (bitflood_amd/lib/*.o, the library's own source list) into
 // tools/build/experimental/liblbfhash.so; at load time it points
 // lbf::g_extra_variants at the table below, so lbf_set_kernel_variant accepts
 // these variants and launch_chunks launches them.  Tools select the library

@@ -3,7 +3,7 @@
 
 A one-shot encode pays for its staging inside its first job: the pinned host
 ring (3 x LBF_PIN_MB) and the HBM batch slots are sized to the work and
-allocated then (lbf_capi.cpp ensure_slot_bytes).  For each size this creates a
+allocated then (staging.cpp ensure_slot_bytes).  For each size this creates a
 new context, times job 1 and job 2 (host memory in, digests out, 256 KiB
 chunks) and reports both rates and the difference in ms.
 Usage: [LBF_LIB=...] python tools/first_pass.py [reps]"""

@@ -1,4 +1,4 @@
-# GPU-box check after host-side changes to lbf_capi.cpp: the host-path GPU tests
+# GPU-box check after host-side changes to bitflood_amd/csrc: the host-path GPU tests
 # (parity, workers, concurrency, C++ suite) and one host-ASAN stress run.
 set -o pipefail
 out=gpurun_out/hardening

@@ -4,6 +4,10 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -DLBF_PC_STAMPS -I../include -I../bitflood_amd/csrc \
 //          probe_pc.hip -o build/probe_pc -L/opt/rocm/lib -lhsa-runtime64
 #include "../bitflood_amd/csrc/lbf_capi.cpp"
+#include "../bitflood_amd/csrc/placement.cpp"
+#include "../bitflood_amd/csrc/staging.cpp"
+#include "../bitflood_amd/csrc/pinning.cpp"
+#include "../bitflood_amd/csrc/wire_batch.cpp"
 #include "../bitflood_amd/csrc/sha1_kernels.hip"
 #include "experimental/sha1_superseded.hip"  // variants 4, 6, 13
 
