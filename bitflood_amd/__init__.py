@@ -9,7 +9,7 @@ Product pieces:
 See DESIGN.md for the path, the boundary and the kernels.
 """
 from . import _capi  # noqa: F401  (imports torch first: one HIP runtime per process)
-from .hashing import (ChunkHasher, DeviceBuffer, LbfError, b64_27, b64_27_decode,  # noqa: F401
-                      chunk_table)
+from .hashing import (STATE_DTYPE, ChunkHasher, DeviceBuffer, LbfError, b64_27, b64_27_decode,  # noqa: F401
+                      chunk_table, new_states)
 
 __version__ = "0.1.0"

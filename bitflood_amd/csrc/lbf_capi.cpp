@@ -177,6 +177,8 @@ extern "C" int lbf_ctx_create(uint32_t device_mask, lbf_ctx** out) {
   KeepCurrentDevice keep;  // worker_init selects each worker's device
   lbf_ctx* ctx = new (std::nothrow) lbf_ctx();
   if (!ctx) return fail(LBF_ERR_NOMEM, "host allocation failed");
+  // piece bytes per launch of lbf_sha1_update_batch: 1 MiB .. 64 GiB
+  ctx->update_bytes = std::max<uint64_t>(1, std::min<uint64_t>(65536, env_u64("LBF_UPDATE_MB", 256))) << 20;
   const int rc = guarded([&] {
     ctx->workers.reserve((size_t)std::min(ndev, 32) * (size_t)per_dev);  // workers never move once initialised
     for (int d = 0; d < ndev && d < 32; ++d) {
@@ -219,8 +221,10 @@ extern "C" int lbf_ctx_worker_info(const lbf_ctx* ctx, int worker, int* device, 
 extern "C" void lbf_ctx_destroy(lbf_ctx* ctx) {
   if (!ctx) return;
   KeepCurrentDevice keep;
-  if (ctx->b64_dev && !ctx->workers.empty() && hipSetDevice(ctx->workers[0].device) == hipSuccess)
-    (void)hipFree(ctx->b64_dev);
+  if ((ctx->b64_dev || ctx->upd_dev) && !ctx->workers.empty() && hipSetDevice(ctx->workers[0].device) == hipSuccess) {
+    if (ctx->b64_dev) (void)hipFree(ctx->b64_dev);
+    if (ctx->upd_dev) (void)hipFree(ctx->upd_dev);
+  }
   for (Worker& w : ctx->workers) worker_free(w);
   for (const Registered& r : ctx->regs)
     if (r.owned) (void)unpin(r.lo);  // teardown: nowhere to report a failure

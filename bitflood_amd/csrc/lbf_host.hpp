@@ -62,6 +62,19 @@ struct PreferNode {
   ~PreferNode();
 };
 
+// Every exit of a synchronous entry point after its first async copy waits for
+// the stream, so no copy is still reading a local staging vector or the
+// caller's (possibly pinned) buffers, or writing into them, once the call has
+// returned.  Declared after the host vectors the copies use, so it
+// runs before they are destroyed.
+struct SyncOnExit {
+  hipStream_t st;
+  ~SyncOnExit() {
+    (void)hipStreamSynchronize(st);
+    (void)hipGetLastError();
+  }
+};
+
 // ---- staging.cpp ------------------------------------------------------------
 // Staging is split in two rings.  A DEVICE slot in HBM holds one batch: the
 // descriptors (offsets u64[cnt], sizes u32[cnt], expected 20 B x cnt, padded
@@ -204,5 +217,11 @@ struct lbf_ctx {
   uint64_t b64_cap = 0;
   // lbf_b64_verify_batch's chunks by decode path (lbf_ctx_b64_stats), guarded by mu
   uint64_t b64_one_pass = 0, b64_general = 0;
+  // lbf_sha1_update_batch's device memory (bytes, states, tables) on worker 0's
+  // device, grown on demand, guarded by mu; and the piece bytes one of its
+  // launches may carry (LBF_UPDATE_MB, read at creation)
+  uint8_t* upd_dev = nullptr;
+  uint64_t upd_cap = 0;
+  uint64_t update_bytes = 256ull << 20;
   mutable std::mutex mu;
 };

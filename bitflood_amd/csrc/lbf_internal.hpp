@@ -35,6 +35,10 @@ struct ChunkParams {
   uint8_t* verdicts;         // n bytes or null
 };
 
+// A device array the caller passed must fit in the allocation it points into
+// (sha1_kernels.hip); LBF_OK for null, empty, or memory HIP cannot place.
+int check_fits(const void* p, uint64_t bytes, const char* what);
+
 int pick_variant(uint64_t n);
 int launch_chunks(const ChunkParams& p, hipStream_t stream);
 

@@ -219,17 +219,13 @@ int launch_b64_encode(const uint8_t* data, const uint64_t* data_off, const uint3
   });
 }
 
-}  // namespace lbf
-
-using lbf::fail;
-
 // A device array the caller passed must fit in the allocation it points into:
 // a launch that would run past one (a digest array sized for fewer chunks than
 // the launch writes) is refused before the kernel runs, since an out-of-bounds
 // write is a GPU fault.  Memory HIP cannot place (an allocator it does not
 // track) is not checked; the chunk bytes of a table launch are not either (the
 // offsets are on the device).
-static int check_fits(const void* p, uint64_t bytes, const char* what) {
+int check_fits(const void* p, uint64_t bytes, const char* what) {
   if (!p || bytes == 0) return LBF_OK;
   hipDeviceptr_t base = nullptr;
   size_t size = 0;
@@ -244,6 +240,11 @@ static int check_fits(const void* p, uint64_t bytes, const char* what) {
                                      " bytes left)");
   return LBF_OK;
 }
+
+}  // namespace lbf
+
+using lbf::check_fits;
+using lbf::fail;
 
 static int check_out_alignment(const uint8_t* d_digests, const uint8_t* d_expected) {
   if ((reinterpret_cast<uintptr_t>(d_digests) & 3u) || (reinterpret_cast<uintptr_t>(d_expected) & 3u))

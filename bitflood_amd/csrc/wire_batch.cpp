@@ -28,19 +28,6 @@ int b64_scratch(lbf_ctx* ctx, uint64_t need, const char* who) {
   return LBF_OK;
 }
 
-// Every exit of a base64 entry point after its first async copy waits for the
-// stream, so no copy is still reading a local staging vector or the caller's
-// (possibly pinned) buffers, or writing into them, once the call has returned
-// (ADVICE r04).  Declared after the host vectors the copies use, so it runs
-// before they are destroyed.
-struct SyncOnExit {
-  hipStream_t st;
-  ~SyncOnExit() {
-    (void)hipStreamSynchronize(st);
-    (void)hipGetLastError();
-  }
-};
-
 // The runs of caller slots a D2H writes (stage_plan.hpp, slot_runs).
 int checked_slot_runs(const uint64_t* off, const uint64_t* len, uint64_t n, const char* who,
                       std::vector<SlotRun>& runs) {

@@ -11,6 +11,9 @@ own call sites:
 * ``ChunkHasher.verify_chunks`` == the compare-with-flood-file verify of
   ``Flood::_SetupFilesAndChunks`` (Flood.cpp:259-275) and of
   ``ChunkMethodHandler::_HandleSendChunk`` (ChunkMethods.cpp:165-167).
+* ``ChunkHasher.update_chunks`` with ``new_states`` == the hash object
+  underneath, fed piece by piece: Crypto++'s ``Update()`` ... ``Final()``
+  (iterhash.cpp:9-99) as one resumable 96-byte state per chain.
 
 All hashing runs on the GPU; there is no CPU path in this module.
 """
@@ -29,6 +32,20 @@ DIGEST = 20
 # pointer for batches over empty data (every chunk then has size 0, so nothing
 # is read from it, but the library still gets a real address).
 _EMPTY = (ctypes.c_uint8 * 1)()
+
+
+# lbf_sha1_state (lbf_hash.h): one resumable SHA-1 chain, 96 bytes.
+STATE_DTYPE = np.dtype({"names": ["h", "buffered", "total", "block"],
+                        "formats": [(np.uint32, 5), np.uint32, np.uint64, (np.uint8, 64)],
+                        "offsets": [0, 20, 24, 32], "itemsize": 96})
+
+
+def new_states(n: int) -> np.ndarray:
+    """n fresh states, as lbf_sha1_state_init leaves them (host code, no GPU)."""
+    states = np.zeros(int(n), dtype=STATE_DTYPE)
+    if states.size:
+        load().lbf_sha1_state_init(states.ctypes.data, states.size)
+    return states
 
 
 def b64_27(digest: bytes) -> str:
@@ -174,6 +191,41 @@ class ChunkHasher:
         check(self._lib.lbf_verify_batch(self._h, base, buf.size, offs.ctypes.data, szs.ctypes.data, n,
                                          exp.ctypes.data, ver.ctypes.data, LBF_HOST_PTR))
         return ver.astype(bool)
+
+    # -- chunks hashed piece by piece (lbf_sha1_update_batch) -------------------
+    def update_chunks(self, states, data, offsets, sizes, state_of=None, final=None, expected=None) -> np.ndarray:
+        """Absorb piece i = data[offsets[i], + sizes[i]) into states[state_of[i]]
+        (states[i] without state_of); `states` (from new_states, or restored
+        from bytes) is updated in place.  A piece with final[i] set ends its
+        chain, as Crypto++'s Final() does (iterhash.cpp:86-99): its digest is
+        row i of the (n, 20) result and its state is fresh again; rows of the
+        other pieces are zero.  With `expected` the result is the bool verdicts
+        instead (False for pieces that are not final)."""
+        if not (isinstance(states, np.ndarray) and states.dtype == STATE_DTYPE and states.ndim == 1
+                and states.flags.c_contiguous and states.flags.writeable):
+            raise ValueError("states must be a writable C-contiguous 1-d array of STATE_DTYPE")
+        buf = _as_u8(data)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        szs = np.ascontiguousarray(sizes, dtype=np.uint32)
+        n = offs.size
+        if szs.size != n:
+            raise ValueError("offsets and sizes differ in length")
+        so = None if state_of is None else np.ascontiguousarray(state_of, dtype=np.uint32)
+        fin = None if final is None else np.ascontiguousarray(final).astype(bool).astype(np.uint8)
+        exp = None if expected is None else np.ascontiguousarray(expected, dtype=np.uint8).reshape(-1, DIGEST)
+        for a, what in ((so, "state_of"), (fin, "final"), (exp, "expected")):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"{what} differs in length")
+        out = np.zeros((n, DIGEST), dtype=np.uint8)
+        ver = np.zeros(n, dtype=np.uint8)
+        if n:
+            base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            check(self._lib.lbf_sha1_update_batch(self._h, states.ctypes.data, states.size, ptr(so), base, buf.size,
+                                                  offs.ctypes.data, szs.ctypes.data, ptr(fin), n,
+                                                  None if exp is not None else out.ctypes.data, ptr(exp),
+                                                  None if exp is None else ver.ctypes.data))
+        return out if exp is None else ver.astype(bool)
 
     # -- chunks read straight from a file (lbf_file_ranges) ---------------------
     def hash_file(self, path: str, offsets, sizes) -> np.ndarray:
@@ -379,6 +431,15 @@ def batch_launch(base, offsets, sizes, n, digests, expected=None, verdicts=None,
                                  stream))
 
 
+def update_launch(states, n_states, state_of, base, offsets, sizes, final, n, digests, expected=None, verdicts=None,
+                  stream=None):
+    """lbf_sha1_update_launch: pieces in device memory absorbed into device-resident
+    states, asynchronous on `stream`; state_of, final and the outputs may be None."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_sha1_update_launch(p(states), n_states, p(state_of), p(base), p(offsets), p(sizes), p(final), n,
+                                        p(digests), p(expected), p(verdicts), stream))
+
+
 def synchronize():
     check(load().lbf_device_synchronize())
 
@@ -388,5 +449,5 @@ def set_kernel_variant(v: int):
 
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
-           "uniform_launch", "batch_launch", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

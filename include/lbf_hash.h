@@ -238,6 +238,61 @@ int lbf_set_kernel_variant(int variant);
 int lbf_get_kernel_variant(void);
 int lbf_kernel_for(uint64_t n_chunks);
 
+/* ---- resumable SHA-1: a chunk hashed piece by piece ------------------------
+ * The reference's hash object takes Update() calls of any length and then
+ * Final(), which restarts it (Crypto++ 5.2.1 IteratedHash, iterhash.cpp:9-99,
+ * iterhash.h:120).  A lbf_sha1_state is that object as a plain record: 96
+ * bytes, owned by the caller, copyable (a peer may store it and resume in
+ * another context or process).  Invariant: buffered == total % 64.
+ * lbf_sha1_state_init is host code and needs no GPU. */
+typedef struct lbf_sha1_state {
+  uint32_t h[5];      /* chaining value, native words (sha.cpp:19-26 at start) */
+  uint32_t buffered;  /* 0..63 bytes of an unfinished block held in `block`    */
+  uint64_t total;     /* bytes absorbed so far, the buffered ones included     */
+  uint8_t  block[64]; /* the first `buffered` bytes are meaningful             */
+} lbf_sha1_state;
+void lbf_sha1_state_init(lbf_sha1_state* states, uint64_t n);
+
+/* Device-resident and asynchronous on `stream`, like lbf_sha1_launch: piece i
+ * = d_base[d_offsets[i], + d_sizes[i]) is absorbed into state d_state_of[i]
+ * (state i when d_state_of is NULL) of d_states[0, n_states), which must be
+ * 16-byte aligned.  A piece with d_final[i] != 0 ends its chain: the digest
+ * goes to d_digests + 20*i and/or the verdict against d_expected + 20*i to
+ * d_verdicts[i], and the state is put back to its initial value.  d_final may
+ * be NULL (no piece is final; then no output is needed); d_digests or
+ * d_expected/d_verdicts (which go together) may be NULL.  Digest and verdict
+ * entries of pieces that are not final are left untouched.  A piece whose
+ * state index is >= n_states is skipped (nothing is read or written for it),
+ * and `buffered` is taken & 63, so a corrupt record can never make the kernel
+ * write outside its own 96 bytes.  Two pieces naming ONE state in one launch
+ * is undefined here: memory-safe, but the order they are absorbed in is not
+ * defined (feed a chain's pieces in successive launches, or use the batch call
+ * below, which refuses it).  The arrays are checked against their allocations
+ * as in lbf_sha1_launch. */
+int lbf_sha1_update_launch(lbf_sha1_state* d_states, uint64_t n_states, const uint32_t* d_state_of,
+                           const uint8_t* d_base, const uint64_t* d_offsets, const uint32_t* d_sizes,
+                           const uint8_t* d_final, uint64_t n, uint8_t* d_digests,
+                           const uint8_t* d_expected, uint8_t* d_verdicts, void* stream);
+/* The same over host memory, synchronous on the context's first device: the
+ * touched states and the pieces' bytes (only those, one copy per run of
+ * adjacent pieces) go to the device, one launch absorbs them, states and
+ * results come back.  out_digests / verdicts entries of pieces that are not
+ * final are left untouched.  Checked before any GPU work, each refused with
+ * LBF_ERR_INVALID and a message naming the piece, states and outputs
+ * untouched: a piece outside [base, base + base_len); state_of[i] >= n_states;
+ * two pieces of one state; a state with buffered > 63 or buffered != total %
+ * 64; total + size past 2^61 bytes (the bit count is a 64-bit number).
+ * Device memory per call is bounded: at most LBF_UPDATE_MB MiB of piece bytes
+ * (default 256, read at context creation) go per launch, a larger call runs
+ * as successive launches, and a single piece larger than that is cut at
+ * multiples of 64 bytes and fed over successive launches.  States and results
+ * are written back launch by launch: a HIP failure part-way through such a
+ * call leaves the pieces of the launches before it absorbed. */
+int lbf_sha1_update_batch(lbf_ctx* ctx, lbf_sha1_state* states, uint64_t n_states, const uint32_t* state_of,
+                          const uint8_t* base, uint64_t base_len, const uint64_t* offsets,
+                          const uint32_t* sizes, const uint8_t* final_flags, uint64_t n,
+                          uint8_t* out_digests, const uint8_t* expected, uint8_t* verdicts);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */

@@ -1,0 +1,178 @@
+// update_plan_tests.cpp -- the planner of lbf_sha1_update_batch
+// (bitflood_amd/csrc/update_plan.hpp) on the CPU: every refusal, the cutting
+// of a call into launches, and the packing of a launch into copies.  Includes
+// only that header and links nothing; tests/test_update_cpu.py compiles it with
+// plain g++ and again with -fsanitize=address,undefined and runs both.
+#include "update_plan.hpp"
+
+#include <cstdio>
+#include <cstring>
+
+using namespace lbf;
+
+static int g_fail = 0;
+#define CHECK(cond)                                                                \
+  do {                                                                             \
+    if (!(cond)) {                                                                 \
+      std::fprintf(stderr, "%s:%d CHECK failed: %s\n", __FILE__, __LINE__, #cond); \
+      ++g_fail;                                                                    \
+    }                                                                              \
+  } while (0)
+
+static std::vector<lbf_sha1_state> fresh(size_t n) {
+  std::vector<lbf_sha1_state> s(n);
+  std::memset(s.data(), 0, n * sizeof(lbf_sha1_state));
+  return s;
+}
+
+static void test_refusals() {
+  std::string why;
+  std::vector<lbf_sha1_state> st = fresh(4);
+  const uint64_t offs[3] = {0, 100, 200};
+  const uint32_t sizes[3] = {100, 100, 56};
+  const uint32_t so[3] = {2, 0, 3};
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == kNoPiece);
+  CHECK(update_check(st.data(), 4, nullptr, 256, offs, sizes, 3, why) == kNoPiece);
+  // a piece outside [base, base + base_len): past the end, and an offset past the end with size 0 allowed at the end
+  CHECK(update_check(st.data(), 4, so, 255, offs, sizes, 3, why) == 2 && why.find("outside") != std::string::npos);
+  const uint64_t far[1] = {UINT64_MAX};
+  const uint32_t one[1] = {1};
+  CHECK(update_check(st.data(), 4, nullptr, 256, far, one, 1, why) == 0);
+  const uint64_t at_end[1] = {256};
+  const uint32_t zero[1] = {0};
+  CHECK(update_check(st.data(), 4, nullptr, 256, at_end, zero, 1, why) == kNoPiece);
+  // a state index >= n_states, named or implied
+  const uint32_t so_bad[3] = {2, 4, 3};
+  CHECK(update_check(st.data(), 4, so_bad, 256, offs, sizes, 3, why) == 1 && why.find("state 4") != std::string::npos);
+  CHECK(update_check(st.data(), 2, nullptr, 256, offs, sizes, 3, why) == 2);
+  // two pieces of one state: the later one is named
+  const uint32_t so_dup[3] = {3, 0, 3};
+  CHECK(update_check(st.data(), 4, so_dup, 256, offs, sizes, 3, why) == 2 && why.find("second piece") != std::string::npos);
+  // corrupt states: buffered > 63, buffered != total % 64
+  st[0].buffered = 64;
+  st[0].total = 64;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == 1 && why.find("corrupt") != std::string::npos);
+  st[0].buffered = 5;
+  st[0].total = 70;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == 1);
+  st[0].total = 69;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == kNoPiece);
+  // total + size past 2^61
+  st[0].buffered = 28;
+  st[0].total = kUpdateMaxTotal - 100;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == kNoPiece);  // exactly 2^61
+  st[0].buffered = 0;
+  st[0].total = kUpdateMaxTotal - 64;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == 1 && why.find("2^61") != std::string::npos);
+  st[0].total = UINT64_MAX - 63;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == 1);
+  // an untouched corrupt state does not matter
+  st[0].total = 0;
+  st[1].buffered = 99;
+  CHECK(update_check(st.data(), 4, so, 256, offs, sizes, 3, why) == kNoPiece);
+}
+
+// Every property of a plan: each piece's cuts cover it in order without a gap,
+// fall on 64-byte multiples of the piece, never share a launch, only the last
+// is marked; no launch carries more than the cap (a multiple of 64, at least 64).
+static void check_plan(const std::vector<uint64_t>& offs, const std::vector<uint32_t>& sizes, uint64_t cap,
+                       size_t want_launches) {
+  const std::vector<std::vector<UpdateCut>> plan = update_launches(offs.data(), sizes.data(), offs.size(), cap);
+  std::vector<uint64_t> done(offs.size(), 0);
+  std::vector<bool> ended(offs.size(), false);
+  std::vector<long> last_launch(offs.size(), -1);
+  uint64_t next_piece = 0;
+  for (size_t l = 0; l < plan.size(); ++l) {
+    uint64_t bytes = 0;
+    for (const UpdateCut& c : plan[l]) {
+      CHECK(c.piece < offs.size());
+      CHECK(!ended[c.piece]);
+      CHECK(c.off == offs[c.piece] + done[c.piece]);  // in order, no gap
+      CHECK(done[c.piece] % 64 == 0);                 // cut at a 64-byte multiple of the piece
+      CHECK(last_launch[c.piece] < (long)l);          // cuts of one piece never share a launch
+      if (done[c.piece] == 0) {
+        CHECK(c.piece == next_piece);  // pieces in caller order
+        ++next_piece;
+      }
+      last_launch[c.piece] = (long)l;
+      done[c.piece] += c.size;
+      CHECK(c.last == (done[c.piece] == sizes[c.piece]));
+      if (c.last) ended[c.piece] = true;
+      bytes += c.size;
+    }
+    CHECK(bytes <= std::max<uint64_t>(64, cap & ~63ull));  // the cap as the planner rounds it
+    CHECK(!plan[l].empty() || plan.size() == 1);
+  }
+  for (size_t i = 0; i < offs.size(); ++i) CHECK(ended[i] && done[i] == sizes[i]);
+  CHECK(plan.size() == want_launches);
+}
+
+static void test_cutting() {
+  const uint64_t MiB = 1 << 20;
+  // the issue's pieces under a 1 MiB cap, one call
+  std::vector<uint32_t> sizes = {0, 1, 64, (uint32_t)MiB - 1, (uint32_t)MiB, (uint32_t)MiB + 65, 3 * (uint32_t)MiB};
+  std::vector<uint64_t> offs;
+  uint64_t at = 7;
+  for (uint32_t s : sizes) {
+    offs.push_back(at);
+    at += s;
+  }
+  // launches: {0, 1, 64, MiB-1 does not fit -> next}, {MiB-1}, {MiB}, {MiB+65: MiB | 65}, {3 MiB: MiB-128 | MiB | MiB | 128}
+  //   = [0,1,64] [MiB-1] [MiB] [cut MiB] [65, cut MiB-128 (room floor64(MiB-65))] [MiB] [MiB] [128]
+  check_plan(offs, sizes, MiB, 8);
+  // each alone
+  for (size_t k = 0; k < sizes.size(); ++k) {
+    const size_t want = sizes[k] <= MiB ? 1 : (sizes[k] + MiB - 1) / MiB;
+    check_plan({offs[k]}, {sizes[k]}, MiB, want);
+  }
+  // a cap that is no multiple of 64 is rounded down; tiny caps still make progress
+  check_plan({0}, {1000}, 200, 6);  // 192-byte launches: 5 full + 40
+  check_plan({0, 1000}, {1000, 30}, 1, 17);  // 64-byte launches: 15 full + 40, then 30 no longer fits beside the 40
+  // nothing to do
+  CHECK(update_launches(nullptr, nullptr, 0, MiB).size() == 1);
+  // many small pieces fill launches without cutting
+  std::vector<uint64_t> o2;
+  std::vector<uint32_t> s2;
+  for (int k = 0; k < 100; ++k) o2.push_back(k * 40000ull), s2.push_back(40000);
+  check_plan(o2, s2, MiB, 4);  // 26 pieces per launch
+  for (const auto& l : update_launches(o2.data(), s2.data(), 100, MiB))
+    for (const UpdateCut& c : l) CHECK(c.last && c.size == 40000);
+}
+
+static void test_runs() {
+  // adjacent pieces travel in one copy; a gap starts another at the source's 16-byte phase; empty pieces take none
+  std::vector<UpdateCut> cuts = {{0, 5, 100, true},   {1, 105, 0, true},  {2, 105, 50, true},
+                                 {3, 1000, 10, true}, {4, 155, 5, true}, {5, 1003, 20, true}};
+  std::vector<Run> runs;
+  std::vector<uint64_t> dev;
+  const uint64_t area = update_runs(cuts, runs, dev);
+  CHECK(runs.size() == 4);
+  CHECK(runs[0].src == 5 && runs[0].len == 150 && runs[0].dst % 16 == 5);
+  CHECK(runs[1].src == 1000 && runs[1].len == 10 && runs[1].dst % 16 == 1000 % 16 && runs[1].dst >= runs[0].dst + 150);
+  CHECK(runs[2].src == 155 && runs[2].len == 5 && runs[2].dst % 16 == 155 % 16 && runs[2].dst >= runs[1].dst + 10);
+  // 1003 lies inside run 1, but only the current run is extended
+  CHECK(runs[3].src == 1003 && runs[3].len == 20 && runs[3].dst % 16 == 1003 % 16 && runs[3].dst >= runs[2].dst + 5);
+  CHECK(dev[0] == runs[0].dst && dev[2] == runs[0].dst + 100 && dev[3] == runs[1].dst && dev[4] == runs[2].dst &&
+        dev[5] == runs[3].dst);
+  CHECK(area == runs[3].dst + 20);
+  // only pieces' bytes are read: no gap is copied along
+  uint64_t sum = 0;
+  for (const Run& r : runs) sum += r.len;
+  CHECK(sum == 100 + 50 + 10 + 5 + 20);
+  // a piece that starts inside the current run shares its bytes
+  std::vector<UpdateCut> over = {{0, 64, 100, true}, {1, 100, 100, true}};
+  update_runs(over, runs, dev);
+  CHECK(runs.size() == 1 && runs[0].len == 136 && dev[1] == dev[0] + 36);
+}
+
+int main() {
+  test_refusals();
+  test_cutting();
+  test_runs();
+  if (g_fail) {
+    std::fprintf(stderr, "%d check(s) failed\n", g_fail);
+    return 1;
+  }
+  std::printf("update_plan_tests: OK\n");
+  return 0;
+}
