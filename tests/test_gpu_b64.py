@@ -4,68 +4,21 @@ A SendChunk frame carries the chunk as XML-RPC base64 text
 (/root/reference/cpp/src/ChunkMethods.cpp:141-163), written by xmlrpc++ 0.7's
 encoder with a newline after every 18 groups (base64.h:154-210; the frame turns
 it into a space, PeerConnection.cpp:132-156) and read back by its decoder
-(base64.h:215-330).  `b64get` below restates that decoder in Python (the same
-rules bitflood_amd/host/PeerWire.cpp Base64Get restates in C++); the GPU's
+(base64.h:215-330).  `b64get` (tests/wire_layouts.py) restates that decoder in
+Python (the same rules bitflood_amd/host/PeerWire.cpp Base64Get restates in
+C++; tests/test_wire_layouts.py pins both to the reference's own); the GPU's
 decoded bytes, lengths and verdicts must equal it on well-formed frames of
 every size up to a full C5 chunk and on texts with junk characters, '='
 anywhere, dropped characters and truncation.
 """
-import base64
 import hashlib
 
 import numpy as np
 import pytest
 
+from tests.wire_layouts import _DEC, SKIP, b64get, xmlrpc_text  # shared with tests/test_gpu_wire.py
+
 pytestmark = pytest.mark.gpu
-
-EQ, SKIP = 64, 255
-_DEC = np.full(256, SKIP, dtype=np.int16)
-for _i, _c in enumerate(b"ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/"):
-    _DEC[_c] = _i
-_DEC[ord("=")] = EQ
-
-
-def b64get(text: bytes) -> bytes:
-    """xmlrpc++ 0.7 base64 decode (base64.h:215-330): skip characters outside
-    the alphabet; take the rest four at a time; a group holding '=' ends the
-    data ("xx==" one byte, "xxx=" two); an incomplete last group is dropped."""
-    v = _DEC[np.frombuffer(text, dtype=np.uint8)]
-    s = v[v != SKIP]
-    out = bytearray()
-    i = 0
-    while True:
-        if i >= len(s) or s[i] == EQ:
-            return bytes(out)
-        if i + 1 >= len(s) or s[i + 1] == EQ:
-            return bytes(out)
-        c0, c1 = int(s[i]), int(s[i + 1])
-        if i + 2 >= len(s):
-            return bytes(out)
-        c2 = int(s[i + 2])
-        if c2 == EQ:
-            out.append(((c0 << 2) | (c1 >> 4)) & 255)
-            return bytes(out)
-        if i + 3 >= len(s):
-            return bytes(out)
-        c3 = int(s[i + 3])
-        if c3 == EQ:
-            out += bytes([((c0 << 2) | (c1 >> 4)) & 255, ((c1 << 4) | (c2 >> 2)) & 255])
-            return bytes(out)
-        out += bytes([((c0 << 2) | (c1 >> 4)) & 255, ((c1 << 4) | (c2 >> 2)) & 255, ((c2 << 6) | c3) & 255])
-        i += 4
-
-
-def xmlrpc_text(data: bytes) -> bytes:
-    """The payload text of a SendChunk frame: base64 with a newline after
-    every 18th complete group (base64.h:197-205), CR/LF framed as spaces."""
-    s = base64.b64encode(data)
-    full = len(data) // 3
-    parts = []
-    for g in range(len(s) // 4):
-        parts.append(s[4 * g:4 * g + 4])
-        if g < full and g % 18 == 17:
-            parts.append(b" ")
-    return b"".join(parts)
 
 
 def _batch(hasher, texts, datas, align=16, shift=0, with_out=True, sizes=None):
