@@ -9,7 +9,7 @@ Product pieces:
 See DESIGN.md for the path, the boundary and the kernels.
 """
 from . import _capi  # noqa: F401  (imports torch first: one HIP runtime per process)
-from .hashing import (STATE_DTYPE, ChunkHasher, DeviceBuffer, LbfError, b64_27, b64_27_decode,  # noqa: F401
-                      chunk_table, new_states)
+from .hashing import (B64_STATE_DTYPE, STATE_DTYPE, ChunkHasher, DeviceBuffer, LbfError, b64_27,  # noqa: F401
+                      b64_27_decode, b64_update_launch, chunk_table, new_b64_states, new_states)
 
 __version__ = "0.1.0"

@@ -82,6 +82,14 @@ _SIGS = {
     "lbf_sha1_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                          _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_b64_state_init": (None, [_c.c_void_p, _c.c_uint64]),
+    "lbf_b64_update_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                         _c.c_void_p]),
+    "lbf_b64_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                        _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                        _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_set_kernel_variant": (_c.c_int, [_c.c_int]),
     "lbf_get_kernel_variant": (_c.c_int, []),
     "lbf_kernel_for": (_c.c_int, [_c.c_uint64]),

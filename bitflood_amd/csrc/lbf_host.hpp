@@ -75,6 +75,23 @@ struct SyncOnExit {
   }
 };
 
+// A call's device memory that a context keeps between calls (lbf_ctx::b64_dev,
+// upd_dev): one allocation on the current device, replaced by one of `want`
+// bytes when `need` does not fit; the caller holds ctx->mu and names itself in
+// `who` for the message.
+inline int grow_scratch(uint8_t*& dev, uint64_t& cap, uint64_t need, uint64_t want, const char* who) {
+  if (need <= cap) return LBF_OK;
+  if (dev) (void)hipFree(dev);
+  dev = nullptr;
+  cap = 0;
+  if (hipMalloc(reinterpret_cast<void**>(&dev), want) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(LBF_ERR_NOMEM, std::string(who) + ": device allocation of " + std::to_string(want) + " bytes");
+  }
+  cap = want;
+  return LBF_OK;
+}
+
 // ---- staging.cpp ------------------------------------------------------------
 // Staging is split in two rings.  A DEVICE slot in HBM holds one batch: the
 // descriptors (offsets u64[cnt], sizes u32[cnt], expected 20 B x cnt, padded

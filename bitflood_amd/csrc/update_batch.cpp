@@ -21,17 +21,7 @@ uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 // The call's device memory: one allocation on worker 0's device (current when
 // this runs), grown on demand; the caller holds ctx->mu.
 int update_scratch(lbf_ctx* ctx, uint64_t need) {
-  if (need <= ctx->upd_cap) return LBF_OK;
-  if (ctx->upd_dev) (void)hipFree(ctx->upd_dev);
-  ctx->upd_dev = nullptr;
-  ctx->upd_cap = 0;
-  const uint64_t want = up(need, 1ull << 20);
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->upd_dev), want) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(LBF_ERR_NOMEM, "lbf_sha1_update_batch: device allocation of " + std::to_string(want) + " bytes");
-  }
-  ctx->upd_cap = want;
-  return LBF_OK;
+  return grow_scratch(ctx->upd_dev, ctx->upd_cap, need, up(need, 1ull << 20), "lbf_sha1_update_batch");
 }
 
 struct UpdateCall {

@@ -15,17 +15,7 @@ namespace {
 // The device memory of the two base64 entry points: one allocation on worker
 // 0's device (current when this runs), grown on demand; the caller holds ctx->mu.
 int b64_scratch(lbf_ctx* ctx, uint64_t need, const char* who) {
-  if (need <= ctx->b64_cap) return LBF_OK;
-  if (ctx->b64_dev) (void)hipFree(ctx->b64_dev);
-  ctx->b64_dev = nullptr;
-  ctx->b64_cap = 0;
-  const uint64_t want = std::max<uint64_t>(need, 64ull << 20);
-  if (hipMalloc(reinterpret_cast<void**>(&ctx->b64_dev), want) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(LBF_ERR_NOMEM, std::string(who) + ": device allocation of " + std::to_string(want) + " bytes");
-  }
-  ctx->b64_cap = want;
-  return LBF_OK;
+  return grow_scratch(ctx->b64_dev, ctx->b64_cap, need, std::max<uint64_t>(need, 64ull << 20), who);
 }
 
 // The runs of caller slots a D2H writes (stage_plan.hpp, slot_runs).

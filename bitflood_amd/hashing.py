@@ -14,6 +14,10 @@ own call sites:
 * ``ChunkHasher.update_chunks`` with ``new_states`` == the hash object
   underneath, fed piece by piece: Crypto++'s ``Update()`` ... ``Final()``
   (iterhash.cpp:9-99) as one resumable 96-byte state per chain.
+* ``ChunkHasher.update_text`` with ``new_b64_states`` == xmlrpc++'s base64
+  decoder (base64.h:215-330) in front of that object, fed the pieces of a
+  SendChunk payload's text as they arrive (ChunkMethods.cpp:137-167): a
+  16-byte decoder state beside each chain's hash state.
 
 All hashing runs on the GPU; there is no CPU path in this module.
 """
@@ -45,6 +49,21 @@ def new_states(n: int) -> np.ndarray:
     states = np.zeros(int(n), dtype=STATE_DTYPE)
     if states.size:
         load().lbf_sha1_state_init(states.ctypes.data, states.size)
+    return states
+
+
+# lbf_b64_state (lbf_hash.h): xmlrpc++'s base64 decoder stopped between two
+# pieces of a chunk's text, 16 bytes, the partner of the chain's STATE_DTYPE record.
+B64_STATE_DTYPE = np.dtype({"names": ["decoded", "carry", "ncarry", "ended", "zero"],
+                            "formats": [np.uint64, np.uint32, np.uint8, np.uint8, np.uint16],
+                            "offsets": [0, 8, 12, 13, 14], "itemsize": 16})
+
+
+def new_b64_states(n: int) -> np.ndarray:
+    """n fresh decoder states, as lbf_b64_state_init leaves them (host code, no GPU)."""
+    states = np.empty(int(n), dtype=B64_STATE_DTYPE)
+    if states.size:
+        load().lbf_b64_state_init(states.ctypes.data, states.size)
     return states
 
 
@@ -226,6 +245,54 @@ class ChunkHasher:
                                                   None if exp is not None else out.ctypes.data, ptr(exp),
                                                   None if exp is None else ver.ctypes.data))
         return out if exp is None else ver.astype(bool)
+
+    # -- chunks' base64 text decoded and hashed piece by piece (lbf_b64_update_batch)
+    def update_text(self, b64_states, sha_states, text, text_offsets, text_lens, out, out_offsets, expected_sizes,
+                    state_of=None, final=None, expected=None):
+        """Piece i = the base64 text text[text_offsets[i], + text_lens[i]) continues
+        chain state_of[i] (chain i without state_of): the pair b64_states[s],
+        sha_states[s] (from new_b64_states / new_states, or restored from bytes),
+        updated in place.  Its chunk is expected_sizes[i] bytes at
+        out[out_offsets[i] ..); the bytes the piece decodes land there at their
+        place in the chunk, and no other byte of `out` is written.  A piece with
+        final[i] set ends its chain.  Returns (out_sizes, verdicts): for a final
+        piece the decoded length (expected_sizes[i] + 1 when more) and, with
+        `expected`, whether length and SHA-1 are the chunk's; entries of the other
+        pieces are 0 / False."""
+        for st, dt, what in ((b64_states, B64_STATE_DTYPE, "b64_states"), (sha_states, STATE_DTYPE, "sha_states")):
+            if not (isinstance(st, np.ndarray) and st.dtype == dt and st.ndim == 1 and st.flags.c_contiguous
+                    and st.flags.writeable):
+                raise ValueError(f"{what} must be a writable C-contiguous 1-d array of its state dtype")
+        if b64_states.size != sha_states.size:
+            raise ValueError("b64_states and sha_states differ in length")
+        if not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags.c_contiguous
+                and out.flags.writeable):
+            raise ValueError("out must be a writable C-contiguous uint8 array")
+        buf = _as_u8(text)
+        toff = np.ascontiguousarray(text_offsets, dtype=np.uint64)
+        tlen = np.ascontiguousarray(text_lens, dtype=np.uint32)
+        ooff = np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        esz = np.ascontiguousarray(expected_sizes, dtype=np.uint32)
+        n = toff.size
+        if not (tlen.size == ooff.size == esz.size == n):
+            raise ValueError("text_offsets, text_lens, out_offsets and expected_sizes differ in length")
+        so = None if state_of is None else np.ascontiguousarray(state_of, dtype=np.uint32)
+        fin = None if final is None else np.ascontiguousarray(final).astype(bool).astype(np.uint8)
+        exp = None if expected is None else np.ascontiguousarray(expected, dtype=np.uint8).reshape(-1, DIGEST)
+        for a, what in ((so, "state_of"), (fin, "final"), (exp, "expected")):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"{what} differs in length")
+        sizes = np.zeros(n, dtype=np.uint32)
+        ver = np.zeros(n, dtype=np.uint8)
+        if n:
+            base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            check(self._lib.lbf_b64_update_batch(self._h, b64_states.ctypes.data, sha_states.ctypes.data,
+                                                 b64_states.size, ptr(so), base, buf.size, toff.ctypes.data,
+                                                 tlen.ctypes.data, ptr(fin), n, esz.ctypes.data, ptr(exp),
+                                                 out.ctypes.data if out.size else None, out.size, ooff.ctypes.data,
+                                                 sizes.ctypes.data, None if exp is None else ver.ctypes.data))
+        return sizes, ver.astype(bool)
 
     # -- chunks read straight from a file (lbf_file_ranges) ---------------------
     def hash_file(self, path: str, offsets, sizes) -> np.ndarray:
@@ -440,6 +507,18 @@ def update_launch(states, n_states, state_of, base, offsets, sizes, final, n, di
                                         p(digests), p(expected), p(verdicts), stream))
 
 
+def b64_update_launch(b64_states, sha_states, n_states, state_of, text, text_offsets, text_lens, final, n, out,
+                      out_offsets, caps, out_sizes, digests, expected, verdicts, piece_offsets, piece_sizes,
+                      stream=None):
+    """lbf_b64_update_launch: pieces of text in device memory decoded into their
+    chunks' slots and absorbed into device-resident state pairs, asynchronous on
+    `stream`; state_of, final, digests and expected/verdicts may be None."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_b64_update_launch(p(b64_states), p(sha_states), n_states, p(state_of), p(text), p(text_offsets),
+                                       p(text_lens), p(final), n, p(out), p(out_offsets), p(caps), p(out_sizes),
+                                       p(digests), p(expected), p(verdicts), p(piece_offsets), p(piece_sizes), stream))
+
+
 def synchronize():
     check(load().lbf_device_synchronize())
 
@@ -449,5 +528,6 @@ def set_kernel_variant(v: int):
 
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
-           "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
+           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -1,5 +1,7 @@
 // PieceHasher.cpp -- libBitFlood::PieceHasher: per-slot resumable SHA-1 states
-// fed through lbf_sha1_update_batch, one GPU call per Update().
+// fed through lbf_sha1_update_batch, one GPU call per Update(), and per-slot
+// base64 decoder states beside them fed through lbf_b64_update_batch, one GPU
+// call per UpdateText().
 #include "libBitFlood/PieceHasher.H"
 
 #include "lbf_hash.h"
@@ -8,8 +10,12 @@
 namespace libBitFlood {
 
 PieceHasher::PieceHasher(U32 i_slots, lbf_ctx* i_ctx)
-    : m_ctx(i_ctx), m_slots(i_slots), m_states(new lbf_sha1_state[i_slots ? i_slots : 1]) {
+    : m_ctx(i_ctx),
+      m_slots(i_slots),
+      m_states(new lbf_sha1_state[i_slots ? i_slots : 1]),
+      m_text_states(new lbf_b64_state[i_slots ? i_slots : 1]) {
   lbf_sha1_state_init(m_states.get(), m_slots);
+  lbf_b64_state_init(m_text_states.get(), m_slots);
 }
 
 PieceHasher::~PieceHasher() {}
@@ -49,10 +55,55 @@ Error::ErrorCode PieceHasher::Update(const U8* i_arena, U64 i_arena_len, const V
   return Error::NO_ERROR_LBF;
 }
 
-U64 PieceHasher::BytesIn(U32 i_slot) const { return i_slot < m_slots ? m_states[i_slot].total : 0; }
+Error::ErrorCode PieceHasher::UpdateText(const char* i_text, U64 i_text_len, const V_TextPiece& i_pieces,
+                                         U8* io_arena, U64 i_arena_len, const V_String& i_expected_hashes,
+                                         std::vector<U8>& o_verdicts, std::vector<U32>* o_sizes) {
+  const U64 n = i_pieces.size();
+  o_verdicts.assign(n, 0);
+  if (o_sizes) o_sizes->assign(n, 0);
+  if (n == 0) return Error::NO_ERROR_LBF;
+  if (i_expected_hashes.size() != n) return Error::UNKNOWN_ERROR_LBF;
+  const std::shared_ptr<lbf_ctx> held = Ctx();  // alive for the whole call
+  if (!held) return Error::UNKNOWN_ERROR_LBF;
+  V_U32 slot(n), lens(n), caps(n), sizes(n, 0);
+  V_U64 toffs(n), ooffs(n);
+  V_U8 last(n), expected(20 * n, 0);
+  for (U64 k = 0; k < n; ++k) {
+    const TextPiece& p = i_pieces[k];
+    slot[k] = p.m_slot;
+    toffs[k] = p.m_text_offset;
+    lens[k] = p.m_text_len;
+    ooffs[k] = p.m_out_offset;
+    caps[k] = p.m_chunk_size;
+    last[k] = p.m_last ? 1 : 0;
+    // a string that is no hash string can match nothing: the call fails before any GPU work
+    if (p.m_last && lbf_b64_27_decode(i_expected_hashes[k].data(), i_expected_hashes[k].size(), &expected[20 * k]) !=
+                        LBF_OK)
+      return Error::UNKNOWN_ERROR_LBF;
+  }
+  static const char kNoText = 0;  // empty text still gets a real address
+  if (lbf_b64_update_batch(held.get(), m_text_states.get(), m_states.get(), m_slots, slot.data(),
+                           i_text ? i_text : &kNoText, i_text ? i_text_len : 0, toffs.data(), lens.data(),
+                           last.data(), n, caps.data(), expected.data(), io_arena, io_arena ? i_arena_len : 0,
+                           ooffs.data(), sizes.data(), o_verdicts.data()) != LBF_OK)
+    return Error::UNKNOWN_ERROR_LBF;
+  for (U64 k = 0; k < n; ++k)
+    if (!last[k]) o_verdicts[k] = 0;
+  if (o_sizes) *o_sizes = sizes;
+  return Error::NO_ERROR_LBF;
+}
+
+U64 PieceHasher::BytesIn(U32 i_slot) const {
+  if (i_slot >= m_slots) return 0;
+  // a slot fed text counts what the text decoded to, the bytes past the chunk's size included
+  return m_states[i_slot].total > m_text_states[i_slot].decoded ? m_states[i_slot].total
+                                                                : m_text_states[i_slot].decoded;
+}
 
 void PieceHasher::Reset(U32 i_slot) {
-  if (i_slot < m_slots) lbf_sha1_state_init(&m_states[i_slot], 1);
+  if (i_slot >= m_slots) return;
+  lbf_sha1_state_init(&m_states[i_slot], 1);
+  lbf_b64_state_init(&m_text_states[i_slot], 1);
 }
 
 }  // namespace libBitFlood

@@ -293,6 +293,85 @@ int lbf_sha1_update_batch(lbf_ctx* ctx, lbf_sha1_state* states, uint64_t n_state
                           const uint32_t* sizes, const uint8_t* final_flags, uint64_t n,
                           uint8_t* out_digests, const uint8_t* expected, uint8_t* verdicts);
 
+/* ---- resumable base64 decode chained to the resumable SHA-1 ----------------
+ * A SendChunk payload is base64 text (ChunkMethods.cpp:137-167) and reaches a
+ * receiver in pieces, as the socket delivers them.  A lbf_b64_state is
+ * xmlrpc++ 0.7's decoder (base64.h:215-330) stopped between two pieces: 16
+ * bytes, owned by the caller, copyable, kept beside the chain's lbf_sha1_state
+ * at the same index of a parallel array.  The rule, for pieces: characters
+ * outside the alphabet are skipped; the carried sextets and the piece's
+ * alphabet characters are taken four at a time; the first '=' ends the data
+ * (one more byte with 2 sextets pending, two with 3, none with 0 or 1) and sets
+ * `ended`, after which text is ignored; an unfinished group is carried, and on
+ * the final piece dropped.  However a text is cut into pieces, the bytes are
+ * those of the whole text's decode.  Invariants (the batch call checks them):
+ * ncarry <= 3, carry < 2^(6*ncarry), ended <= 1, zero == 0, ended == 0 implies
+ * decoded % 3 == 0, decoded < 2^61, and the partner SHA state's total ==
+ * min(decoded, chunk size).  lbf_b64_state_init is host code and needs no GPU. */
+typedef struct lbf_b64_state {
+  uint64_t decoded;  /* bytes the chain's text has decoded to so far (true count, past the slot too) */
+  uint32_t carry;    /* the sextets of the unfinished group: sextet k at bits [6k, 6k+6) */
+  uint8_t  ncarry;   /* 0..3 */
+  uint8_t  ended;    /* 1 once a group holding '=' has ended the data; later text is ignored */
+  uint16_t zero;
+} lbf_b64_state;
+void lbf_b64_state_init(lbf_b64_state* states, uint64_t n);
+
+/* Device-resident and asynchronous on `stream`: three enqueues, no host round
+ * trip.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
+ * continues chain d_state_of[i] (chain i when d_state_of is NULL): the pair
+ * d_b64_states[s], d_sha_states[s] of n_states pairs (both arrays 16-byte
+ * aligned).  Its chunk's slot is d_out[d_out_offsets[i], + d_caps[i]) -- the
+ * caller repeats slot start and chunk size for every piece of a chain -- and
+ * the bytes the piece decodes land in it at their position in the chunk; no
+ * byte at or past d_caps[i] is written.  A first kernel decodes (one workgroup
+ * per piece) and fills the work arrays d_piece_offsets / d_piece_sizes (n
+ * entries each, the caller's) with where each piece's new bytes lie;
+ * lbf_sha1_update_launch absorbs exactly those; a last kernel clears the
+ * verdict of a final piece whose decoded length is not d_caps[i].  A piece
+ * with d_final[i] != 0 ends its chain: an unfinished group is dropped,
+ * d_out_sizes[i] = the decoded length (d_caps[i] + 1 when more), digest and/or
+ * verdict as lbf_sha1_update_launch writes them, and both records are put back
+ * to their initial values.  Entries of pieces that are not final are left
+ * untouched.  d_out_sizes is required; d_final, d_digests and d_expected /
+ * d_verdicts may be NULL as for lbf_sha1_update_launch.  A piece whose state
+ * index is >= n_states is skipped, nothing read or written for it; one whose
+ * d_caps[i] exceeds 1 GiB decodes nothing, hands the hash an empty piece and
+ * gets verdict 0 and d_out_sizes[i] = 0, and when it is final both records are
+ * put back all the same.  A forged record (ncarry is taken & 3, carry masked,
+ * decoded clamped to 2^61, past every slot, so that no position wraps) can
+ * never make the kernel write outside its slot and its records, nor name more
+ * than the slot holds in the piece table.  Two pieces of one chain in one launch are
+ * undefined as for lbf_sha1_update_launch.  Every array is checked against its
+ * allocation. */
+int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
+                          const uint32_t* d_state_of, const char* d_text, const uint64_t* d_text_offsets,
+                          const uint32_t* d_text_lens, const uint8_t* d_final, uint64_t n, uint8_t* d_out,
+                          const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
+                          uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
+                          uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, void* stream);
+/* The same over host memory, synchronous on the context's first device.  Piece
+ * i = text[text_offsets[i], + text_lens[i]) of chain state_of[i], whose chunk
+ * is expected_sizes[i] bytes and lives at out[out_offsets[i], +
+ * expected_sizes[i]).  Checked before any GPU work, each refused with
+ * LBF_ERR_INVALID and a message naming the piece, states and outputs
+ * untouched: text outside [text, text + text_len); a slot outside out; a state
+ * index out of range; two pieces of one state; a broken invariant of either
+ * record; a chunk over 1 GiB; slots of different states that overlap.  At most
+ * LBF_UPDATE_MB MiB of text go to the device per launch (a larger piece is cut
+ * and fed over successive launches).  What comes back: only the bytes this
+ * call decoded, at out[out_offsets[i] + bytes decoded before ..) -- no other
+ * byte of `out` is written, and nothing is zero-filled: the bytes that have
+ * not arrived are the caller's -- the states, and for final pieces
+ * out_sizes[i] (may be NULL) and verdicts[i] = 1 when the decoded length is
+ * expected_sizes[i] and the SHA-1 of those bytes equals expected[20*i ..).
+ * expected and verdicts go together and may be NULL. */
+int lbf_b64_update_batch(lbf_ctx* ctx, lbf_b64_state* b64_states, lbf_sha1_state* sha_states, uint64_t n_states,
+                         const uint32_t* state_of, const char* text, uint64_t text_len,
+                         const uint64_t* text_offsets, const uint32_t* text_lens, const uint8_t* final_flags,
+                         uint64_t n, const uint32_t* expected_sizes, const uint8_t* expected, uint8_t* out,
+                         uint64_t out_len, const uint64_t* out_offsets, uint32_t* out_sizes, uint8_t* verdicts);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */

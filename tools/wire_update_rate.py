@@ -1,0 +1,248 @@
+#!/usr/bin/env python3
+"""Rate of the piecewise base64 decode chained to the resumable SHA-1
+(lbf_b64_update_launch), device-resident (diagnostic, not the bench; recorded
+in DESIGN.md §4.7 and §5, not gated).
+
+C2's shape: 16,384 chunks of 256 KiB (lbf_fill_synthetic) as the text
+xmlrpc++'s encoder writes for them (354,382 characters a chunk, built on the
+host slice by slice and uploaded).  One process alternates, round by round,
+  t1   the text as one piece with the final flag (one launch = three kernels)
+  t4   four pieces of a quarter of the text each
+  t64  64 pieces
+  h1, h4, h64   lbf_sha1_update_launch alone over the decoded bytes, cut the same way
+with HIP events on the launch stream around each case's launches, after a
+warm-up, `--rounds` x `--reps` passes per figure; t - h is the decode's share.
+After the warm-up every verdict must be 1, every decoded length the chunk
+size, and the decoded bytes the chunks.
+
+Comparators from another build of the library (LBF_LIB=<its liblbfhash.so>):
+  --hash-only        h1, h4, h64 alone (a library without the text entry points)
+  --general-decode   lbf_b64_verify_batch over 1,024 of the texts with one junk
+                     character in front of each, so that the general two-pass
+                     b64_decode_kernel takes them; the whole host call is timed,
+                     and the kernel's own time is read from a kernel trace
+                     (rocprofv3 --kernel-trace --stats -- python tools/wire_update_rate.py ...)
+
+Run it under a time limit:
+  timeout -k 10 600 python tools/wire_update_rate.py --out profiles/wire_update_rate.json
+"""
+import argparse
+import base64
+import ctypes
+import json
+import os
+import signal
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from bitflood_amd import ChunkHasher, DeviceBuffer, new_states  # noqa: E402
+from bitflood_amd import hashing as H  # noqa: E402
+from bitflood_amd._capi import check, load  # noqa: E402
+
+
+def b64_len(size: int) -> int:
+    return 4 * (size // 3) + (4 if size % 3 else 0) + size // 3 // 18
+
+
+def encoder_text(chunk: np.ndarray) -> np.ndarray:
+    """xmlrpc++'s text of one chunk: base64, a separator after every 18th complete group."""
+    s = np.frombuffer(base64.b64encode(chunk), dtype=np.uint8)
+    lines = chunk.size // 3 // 18
+    out = np.empty(s.size + lines, dtype=np.uint8)
+    body = out[:73 * lines].reshape(lines, 73)
+    body[:, :72] = s[:72 * lines].reshape(lines, 72)
+    body[:, 72] = ord(" ")
+    out[73 * lines:] = s[72 * lines:]
+    return out
+
+
+def general_decode(a):
+    """The comparator for the decode: the general kernel through the host call."""
+    n, cs = min(a.chains, 1024), a.chunk
+    dev = DeviceBuffer(n * cs)
+    dev.fill_synthetic(0x5EED)
+    H.synchronize()
+    data = dev.download(n * cs)
+    dev.free()
+    tl = b64_len(cs) + 1
+    slot = (tl + 15) // 16 * 16
+    text = np.zeros(slot * n, dtype=np.uint8)
+    for i in range(n):
+        text[i * slot] = ord("*")  # outside the encoder's layout: the one-pass decode hands the text on
+        text[i * slot + 1:i * slot + tl] = encoder_text(data[i * cs:(i + 1) * cs])
+    import hashlib
+    exp = np.frombuffer(b"".join(hashlib.sha1(data[i * cs:(i + 1) * cs]).digest() for i in range(n)), np.uint8)
+    toff = np.arange(n, dtype=np.uint64) * np.uint64(slot)
+    out = np.zeros(n * cs, dtype=np.uint8)
+    ooff = np.arange(n, dtype=np.uint64) * np.uint64(cs)
+    with ChunkHasher(device_mask=1) as h:
+        h.verify_b64(text, toff, np.full(n, tl), np.full(n, cs), exp, out, ooff)
+        before = h.b64_stats()
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            ver, dec = h.verify_b64(text, toff, np.full(n, tl), np.full(n, cs), exp, out, ooff)
+        dt = (time.perf_counter() - t0) / a.reps
+        after = h.b64_stats()
+    res = {"mode": "general-decode", "chunks": n, "chunk": cs, "calls": a.reps, "host_call_ms": round(dt * 1e3, 3),
+           "general_chunks_per_call": (after["general"] - before["general"]) // a.reps,
+           "parity": bool(ver.all() and (dec == cs).all() and np.array_equal(out, data))}
+    return res, res["parity"] and res["general_chunks_per_call"] == n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--chains", type=int, default=16384)
+    ap.add_argument("--chunk", type=int, default=262144)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=4, help="passes per case per round")
+    ap.add_argument("--step-timeout", type=int, default=120, help="seconds one case of one round may take")
+    ap.add_argument("--hash-only", action="store_true")
+    ap.add_argument("--general-decode", action="store_true")
+    ap.add_argument("--cases", default="", help="comma-separated subset of the cases (for a kernel trace of one)")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    n, cs = a.chains, a.chunk
+    lib = load()
+    torch.cuda.set_device(0)
+
+    def emit(res, ok):
+        res["library"] = os.environ.get("LBF_LIB", "in-tree")
+        line = json.dumps(res)
+        print(line, flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        return 0 if ok else 1
+
+    if a.general_decode:
+        return emit(*general_decode(a))
+
+    sp = ctypes.c_void_p()
+    check(lib.lbf_stream_create(ctypes.byref(sp)))
+    stream = torch.cuda.ExternalStream(sp.value)
+    tl = b64_len(cs)
+    slot = (tl + 15) // 16 * 16  # every text 16-byte aligned, as a receiver's frame buffer would be
+    parts = (1, 4, 64)
+    bufs = dict(data=DeviceBuffer(n * cs), ref=DeviceBuffer(20 * n), dig=DeviceBuffer(20 * n), sha=DeviceBuffer(96 * n),
+                fin1=DeviceBuffer(n), fin0=DeviceBuffer(n), ver=DeviceBuffer(n))
+    if not a.hash_only:
+        bufs.update(text=DeviceBuffer(n * slot), out=DeviceBuffer(n * cs), b64=DeviceBuffer(16 * n),
+                    ooff=DeviceBuffer(8 * n), caps=DeviceBuffer(4 * n), osz=DeviceBuffer(4 * n),
+                    poff=DeviceBuffer(8 * n), psz=DeviceBuffer(4 * n))
+    try:
+        b = bufs
+        b["data"].fill_synthetic(0x5EED)
+        b["sha"].upload(new_states(n))
+        b["fin1"].upload(np.ones(n, dtype=np.uint8))
+        b["fin0"].upload(np.zeros(n, dtype=np.uint8))
+        H.set_kernel_variant(0)
+        H.uniform_launch(b["data"], n * cs, cs, 0, n, b["ref"])
+        H.synchronize()
+        want = b["ref"].download(20 * n).tobytes()
+        base = np.arange(n, dtype=np.uint64)
+        for p in parts:  # the hash comparator's pieces: the chunk's bytes in p equal parts
+            b["hsz", p] = DeviceBuffer(4 * n)
+            b["hsz", p].upload(np.full(n, cs // p, dtype=np.uint32))
+            for k in range(p):
+                b["hoff", p, k] = DeviceBuffer(8 * n)
+                b["hoff", p, k].upload(base * np.uint64(cs) + np.uint64(k * (cs // p)))
+        if not a.hash_only:
+            from bitflood_amd import new_b64_states
+            b["b64"].upload(new_b64_states(n))
+            b["ooff"].upload(base * np.uint64(cs))
+            b["caps"].upload(np.full(n, cs, dtype=np.uint32))
+            step = 1024  # chunks per host slice
+            for i0 in range(0, n, step):
+                m = min(step, n - i0)
+                host = b["data"].download(m * cs, offset=i0 * cs)
+                text = np.zeros(m * slot, dtype=np.uint8)
+                for i in range(m):
+                    text[i * slot:i * slot + tl] = encoder_text(host[i * cs:(i + 1) * cs])
+                b["text"].upload(text, offset=i0 * slot)
+            for p in parts:  # the text in p parts of (nearly) equal length
+                cut = [k * tl // p for k in range(p + 1)]
+                for k in range(p):
+                    b["toff", p, k], b["tlen", p, k] = DeviceBuffer(8 * n), DeviceBuffer(4 * n)
+                    b["toff", p, k].upload(base * np.uint64(slot) + np.uint64(cut[k]))
+                    b["tlen", p, k].upload(np.full(n, cut[k + 1] - cut[k], dtype=np.uint32))
+
+        def text_pieces(p):
+            def run():
+                for k in range(p):
+                    H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", p, k], b["tlen", p, k],
+                                        b["fin1"] if k == p - 1 else b["fin0"], n, b["out"], b["ooff"], b["caps"],
+                                        b["osz"], b["dig"], b["ref"], b["ver"], b["poff"], b["psz"], stream=sp)
+            return run
+
+        def hash_pieces(p):
+            def run():
+                # the bytes the decode wrote, once a text case has run; the chunks themselves otherwise
+                src = b["out"] if decoded_once else b["data"]
+                for k in range(p):
+                    H.update_launch(b["sha"], n, None, src, b["hoff", p, k], b["hsz", p],
+                                    b["fin1"] if k == p - 1 else b["fin0"], n, b["dig"], b["ref"], b["ver"], stream=sp)
+            return run
+
+        cases = [] if a.hash_only else [(f"t{p}", text_pieces(p), p) for p in parts]
+        cases += [(f"h{p}", hash_pieces(p), p) for p in parts]
+        if a.cases:
+            cases = [c for c in cases if c[0] in a.cases.split(",")]
+        decoded_once = any(name.startswith("t") for name, _, _ in cases)  # the t cases come first
+        probe = min(64 << 20, n * cs)  # the part of the decoded bytes that is compared with the chunks
+        ms = {name: [] for name, _, _ in cases}
+        agree = {}
+
+        def timed(fn, reps):
+            signal.alarm(a.step_timeout)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(reps):
+                fn()
+            e1.record(stream)
+            e1.synchronize()
+            signal.alarm(0)
+            return e0.elapsed_time(e1) / reps
+
+        for name, fn, _ in cases:  # warm-up, and every case's results
+            b["dig"].upload(np.zeros(20 * n, dtype=np.uint8))
+            b["ver"].upload(np.zeros(n, dtype=np.uint8))
+            if name.startswith("t"):
+                b["osz"].upload(np.zeros(n, dtype=np.uint32))
+                b["out"].upload(np.zeros(probe, dtype=np.uint8))
+            timed(fn, 1)
+            ok = b["dig"].download(20 * n).tobytes() == want and bool(b["ver"].download(n).all())
+            if name.startswith("t"):
+                ok = ok and bool((b["osz"].download(4 * n, dtype=np.uint32) == cs).all())
+                ok = ok and b["out"].download(probe).tobytes() == b["data"].download(probe).tobytes()
+            agree[name] = ok
+        for _ in range(a.rounds):
+            for name, fn, _ in cases:
+                ms[name].append(timed(fn, a.reps))
+        gib = n * cs / 2**30
+        res = {"mode": "hash-only" if a.hash_only else "text", "chains": n, "chunk": cs, "text_chars": tl,
+               "gib_decoded": gib, "rounds": a.rounds, "reps": a.reps, "cases": {}}
+        for name, _, launches in cases:
+            med = statistics.median(ms[name])
+            res["cases"][name] = {"launches_per_pass": launches, "ms_per_4gib_median": round(med * 4 / gib, 4),
+                                  "ms_min": round(min(ms[name]) * 4 / gib, 4),
+                                  "ms_max": round(max(ms[name]) * 4 / gib, 4), "results_agree": agree[name]}
+        if not a.hash_only and not a.cases:
+            res["decode_share_ms"] = {f"t{p}": round(res["cases"][f"t{p}"]["ms_per_4gib_median"] -
+                                                     res["cases"][f"h{p}"]["ms_per_4gib_median"], 4) for p in parts}
+        return emit(res, all(agree.values()))
+    finally:
+        for buf in bufs.values():
+            buf.free()
+        check(lib.lbf_stream_destroy(sp))
+
+
+if __name__ == "__main__":
+    sys.exit(main())
