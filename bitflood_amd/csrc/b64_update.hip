@@ -12,11 +12,21 @@
 // lbf_sha1_update_launch absorbs exactly those: the verdict waits only for the
 // last piece's share of the chunk.
 //
+// The kernel here treats a piece as arbitrary text.  The part of a piece that
+// continues the encoder's layout is taken first by b64_update_lines.hip's
+// kernel (unless lbf_set_b64_lines switched it off), which moves the record on
+// and hands over, through the piece table's two arrays, where the chain stood
+// and how many characters it took; this kernel decodes what is left.
+//
 // A translation unit of its own, like sha1_update.hip: the shipped kernels'
 // ISA stays as recorded (tests/test_isa.py).  DESIGN.md §4.7.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <stdlib.h>
 
+#include <atomic>
+
+#include "b64_update_lines.hpp"
 #include "lbf_internal.hpp"
 
 namespace lbf {
@@ -38,6 +48,9 @@ struct B64UpdateParams {
   uint64_t* piece_off;          // the table lbf_sha1_update_launch reads
   uint32_t* piece_size;
   uint8_t* verdicts;            // the last kernel only
+  // the line path ran in front (b64_update_lines.hip): piece_off[i] holds the chain's byte count before the call
+  // and piece_size[i] the characters of the piece already decoded; both are overwritten with their final values
+  uint32_t lines;
 };
 
 constexpr uint32_t kThreads = 256;
@@ -132,15 +145,23 @@ __global__ void __launch_bounds__(kThreads) b64_update_kernel(B64UpdateParams p)
   uint32_t nc = r.w & 3u;
   const uint32_t carry = r.z & ((1u << (6u * nc)) - 1u);
   bool ended = ((r.w >> 8) & 0xFFu) != 0;
-  const uint64_t before = decoded < cap ? decoded : (uint64_t)cap;
+  uint64_t before = decoded < cap ? decoded : (uint64_t)cap;
+  uint32_t taken = 0;
+  if (p.lines) {  // the record has moved on by what the line path took: the piece's share starts where it started
+    const uint64_t b = p.piece_off[i];
+    before = b < cap ? b : (uint64_t)cap;
+    taken = p.piece_size[i];
+  }
 
   tab[threadIdx.x] = g_update_table.v[threadIdx.x];
   if (threadIdx.x < 3) sx[threadIdx.x] = (uint8_t)((carry >> (6u * threadIdx.x)) & 63u);
   if (threadIdx.x == 0) first_eq = 0xFFFFFFFFu;
   __syncthreads();
 
-  const uint8_t* const t = p.text + p.text_off[i];
-  const uint64_t len = ended ? 0 : p.text_len[i];
+  const uint32_t piece_len = p.text_len[i];
+  if (taken > piece_len) taken = piece_len;  // never: the line path takes a prefix
+  const uint8_t* const t = p.text + p.text_off[i] + taken;
+  const uint64_t len = ended ? 0 : piece_len - taken;
   const uint64_t slot = p.out_off[i];  // positions are sums of 64-bit numbers, taken mod 2^64
   for (uint64_t t0 = 0; t0 < len; t0 += kTrip) {
     // 1. sixteen characters per lane; the ragged end reads as junk
@@ -293,12 +314,44 @@ extern "C" void lbf_b64_state_init(lbf_b64_state* states, uint64_t n) {
   }
 }
 
+// The line path's switch: LBF_B64_LINES at first use (default on), then lbf_set_b64_lines.
+static std::atomic<int> g_b64_lines{-1};
+
+bool lbf::b64_lines_enabled() {
+  int v = g_b64_lines.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("LBF_B64_LINES");
+    const int from_env = lbf::kB64LinesDefault ? !(e && e[0] == '0' && e[1] == 0) : (e && e[0] == '1' && e[1] == 0);
+    g_b64_lines.compare_exchange_strong(v, from_env, std::memory_order_relaxed);  // a setter that got in first wins
+    v = g_b64_lines.load(std::memory_order_relaxed);
+  }
+  return v != 0;
+}
+
+extern "C" int lbf_set_b64_lines(int on) {
+  const int before = lbf::b64_lines_enabled() ? 1 : 0;
+  g_b64_lines.store(on ? 1 : 0, std::memory_order_relaxed);
+  return before;
+}
+
 extern "C" int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
                                      const uint32_t* d_state_of, const char* d_text, const uint64_t* d_text_offsets,
                                      const uint32_t* d_text_lens, const uint8_t* d_final, uint64_t n, uint8_t* d_out,
                                      const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
                                      uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                                      uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, void* stream) {
+  return lbf::b64_update_launch_counted(d_b64_states, d_sha_states, n_states, d_state_of, d_text, d_text_offsets,
+                                        d_text_lens, d_final, n, d_out, d_out_offsets, d_caps, d_out_sizes, d_digests,
+                                        d_expected, d_verdicts, d_piece_offsets, d_piece_sizes, nullptr, stream);
+}
+
+int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
+                                   const uint32_t* d_state_of, const char* d_text, const uint64_t* d_text_offsets,
+                                   const uint32_t* d_text_lens, const uint8_t* d_final, uint64_t n, uint8_t* d_out,
+                                   const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
+                                   uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
+                                   uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, uint32_t* d_line_chars,
+                                   void* stream) {
   const std::string who = "lbf_b64_update_launch";
   if (n == 0) return LBF_OK;
   if (!d_b64_states || !d_sha_states || !d_text || !d_text_offsets || !d_text_lens || !d_out || !d_out_offsets ||
@@ -333,6 +386,7 @@ extern "C" int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state
   if (int rc = check_fits(d_verdicts, n, "lbf_b64_update_launch: verdicts")) return rc;
   if (int rc = check_fits(d_piece_offsets, 8 * n, "lbf_b64_update_launch: piece_offsets")) return rc;
   if (int rc = check_fits(d_piece_sizes, 4 * n, "lbf_b64_update_launch: piece_sizes")) return rc;
+  if (int rc = check_fits(d_line_chars, 4 * n, "lbf_b64_update_launch: line_chars")) return rc;
   lbf::B64UpdateParams p{};
   p.b64_states = reinterpret_cast<uint8_t*>(d_b64_states);
   p.n_states = n_states;
@@ -349,6 +403,23 @@ extern "C" int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state
   p.piece_size = d_piece_sizes;
   p.verdicts = d_verdicts;
   hipStream_t st = (hipStream_t)stream;
+  if (lbf::b64_lines_enabled()) {  // the text that continues the encoder's layout, in front of the general rule
+    lbf::B64LinesParams lp{};
+    lp.b64_states = p.b64_states;
+    lp.n_states = n_states;
+    lp.state_of = d_state_of;
+    lp.text = p.text;
+    lp.text_off = d_text_offsets;
+    lp.text_len = d_text_lens;
+    lp.out = d_out;
+    lp.out_off = d_out_offsets;
+    lp.cap = d_caps;
+    lp.before = d_piece_offsets;
+    lp.taken = d_piece_sizes;
+    lp.line_chars = d_line_chars;
+    if (int rc = lbf::launch_b64_update_lines(lp, (uint32_t)n, st)) return rc;
+    p.lines = 1;
+  }
   hipLaunchKernelGGL(lbf::b64_update_kernel, dim3((uint32_t)n), dim3(lbf::kThreads), 0, st, p);
   LBF_HIP_TRY(hipGetLastError());
   if (int rc = lbf_sha1_update_launch(d_sha_states, n_states, d_state_of, d_out, d_piece_offsets, d_piece_sizes,

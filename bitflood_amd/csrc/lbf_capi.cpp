@@ -248,6 +248,14 @@ extern "C" int lbf_ctx_b64_stats(lbf_ctx* ctx, uint64_t* one_pass_chunks, uint64
   return LBF_OK;
 }
 
+extern "C" int lbf_ctx_b64_update_stats(lbf_ctx* ctx, uint64_t* line_chars, uint64_t* scan_chars) {
+  if (!ctx) return fail(LBF_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (line_chars) *line_chars = ctx->b64_line_chars;
+  if (scan_chars) *scan_chars = ctx->b64_scan_chars;
+  return LBF_OK;
+}
+
 extern "C" int lbf_ctx_staging_stats(lbf_ctx* ctx, uint64_t* staged_bytes, uint64_t* direct_bytes) {
   if (!ctx) return fail(LBF_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lock(ctx->mu);  // between jobs

@@ -240,5 +240,7 @@ struct lbf_ctx {
   uint8_t* upd_dev = nullptr;
   uint64_t upd_cap = 0;
   uint64_t update_bytes = 256ull << 20;
+  // lbf_b64_update_batch's characters by decode path (lbf_ctx_b64_update_stats), guarded by mu
+  uint64_t b64_line_chars = 0, b64_scan_chars = 0;
   mutable std::mutex mu;
 };

@@ -149,6 +149,14 @@ class ChunkHasher:
         check(self._lib.lbf_ctx_b64_stats(self._h, ctypes.byref(one), ctypes.byref(gen)))
         return {"one_pass": one.value, "general": gen.value}
 
+    def b64_update_stats(self) -> dict:
+        """Characters of update_text calls so far by decode path: the prefixes
+        that continued the encoder's layout and went through line tiles, and the
+        rest, decoded by the general rule (lbf_ctx_b64_update_stats)."""
+        line, scan = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(self._lib.lbf_ctx_b64_update_stats(self._h, ctypes.byref(line), ctypes.byref(scan)))
+        return {"line_chars": line.value, "scan_chars": scan.value}
+
     # -- caller-pinned sources (lbf_host_register) ---------------------------
     def register_host(self, data) -> None:
         """Pin `data` (a contiguous numpy array / buffer) for this context:
@@ -519,6 +527,12 @@ def b64_update_launch(b64_states, sha_states, n_states, state_of, text, text_off
                                        p(digests), p(expected), p(verdicts), p(piece_offsets), p(piece_sizes), stream))
 
 
+def set_b64_lines(on) -> bool:
+    """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
+    off, process-wide; returns the previous setting."""
+    return bool(load().lbf_set_b64_lines(1 if on else 0))
+
+
 def synchronize():
     check(load().lbf_device_synchronize())
 
@@ -529,5 +543,5 @@ def set_kernel_variant(v: int):
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
-           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

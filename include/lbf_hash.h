@@ -317,15 +317,24 @@ typedef struct lbf_b64_state {
 } lbf_b64_state;
 void lbf_b64_state_init(lbf_b64_state* states, uint64_t n);
 
-/* Device-resident and asynchronous on `stream`: three enqueues, no host round
- * trip.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
+/* Device-resident and asynchronous on `stream`: four enqueues (three with the
+ * line path off, lbf_set_b64_lines), no host round trip, no device
+ * allocation.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
  * continues chain d_state_of[i] (chain i when d_state_of is NULL): the pair
  * d_b64_states[s], d_sha_states[s] of n_states pairs (both arrays 16-byte
  * aligned).  Its chunk's slot is d_out[d_out_offsets[i], + d_caps[i]) -- the
  * caller repeats slot start and chunk size for every piece of a chain -- and
  * the bytes the piece decodes land in it at their position in the chunk; no
- * byte at or past d_caps[i] is written.  A first kernel decodes (one workgroup
- * per piece) and fills the work arrays d_piece_offsets / d_piece_sizes (n
+ * byte at or past d_caps[i] is written, and no byte of the slot other than the
+ * ones the call decodes: what lies below the chain's position and what has not
+ * arrived stay as they are, so slots may be packed next to one another.  The
+ * line path goes first (one workgroup per piece): the prefix of a piece that
+ * continues xmlrpc++'s layout from where the record stands -- groups of four
+ * alphabet characters, a separator after every 18th -- is decoded from its
+ * known places through tiles of whole lines, each tile validated before it is
+ * stored; the record moves on in place and the work arrays carry the count to
+ * the next kernel.  That kernel decodes the rest of every piece by the general
+ * rule (one workgroup per piece) and fills the work arrays d_piece_offsets / d_piece_sizes (n
  * entries each, the caller's) with where each piece's new bytes lie;
  * lbf_sha1_update_launch absorbs exactly those; a last kernel clears the
  * verdict of a final piece whose decoded length is not d_caps[i].  A piece
@@ -350,6 +359,18 @@ int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_sta
                           const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
                           uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                           uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, void* stream);
+/* The line path of lbf_b64_update_launch / lbf_b64_update_batch, process-wide:
+ * 0 switches it off (exactly the three enqueues of the general rule), anything
+ * else on.  Returns the previous value.  Until the first launch or call of
+ * this function the value is LBF_B64_LINES's (default on; "0" = off).  Both
+ * routes give the same bytes, records, lengths and verdicts; the switch exists
+ * so that one process can alternate them. */
+int lbf_set_b64_lines(int on);
+/* Characters of lbf_b64_update_batch calls on this context so far, by decode
+ * path (diagnostics; either pointer may be NULL): their sum is the sum of
+ * text_lens of every accepted call.  The text of a chain that has ended counts
+ * as scan_chars. */
+int lbf_ctx_b64_update_stats(lbf_ctx* ctx, uint64_t* line_chars, uint64_t* scan_chars);
 /* The same over host memory, synchronous on the context's first device.  Piece
  * i = text[text_offsets[i], + text_lens[i]) of chain state_of[i], whose chunk
  * is expected_sizes[i] bytes and lives at out[out_offsets[i], +

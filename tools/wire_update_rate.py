@@ -6,14 +6,19 @@ in DESIGN.md §4.7 and §5, not gated).
 C2's shape: 16,384 chunks of 256 KiB (lbf_fill_synthetic) as the text
 xmlrpc++'s encoder writes for them (354,382 characters a chunk, built on the
 host slice by slice and uploaded).  One process alternates, round by round,
-  t1   the text as one piece with the final flag (one launch = three kernels)
-  t4   four pieces of a quarter of the text each
-  t64  64 pieces
+  t1_lines, t1_scan    the text as one piece with the final flag, with the line
+                       path on (one launch = four kernels) and off (three)
+  t4_lines, t4_scan    four pieces of a quarter of the text each
+  t64_lines, t64_scan  64 pieces
   h1, h4, h64   lbf_sha1_update_launch alone over the decoded bytes, cut the same way
 with HIP events on the launch stream around each case's launches, after a
-warm-up, `--rounds` x `--reps` passes per figure; t - h is the decode's share.
-After the warm-up every verdict must be 1, every decoded length the chunk
-size, and the decoded bytes the chunks.
+warm-up, `--rounds` x `--reps` passes per figure; t - h is the decode's share,
+and a case's spread is its max - min over the rounds.  After the warm-up every
+verdict must be 1, every decoded length the chunk size, and the decoded bytes
+the chunks.  Also reported: the share of each case's characters that the line
+path takes (a sample of the chains through lbf_b64_update_batch, whose context
+counts them), and what the line path's enqueue costs a call (launches of
+empty pieces, on against off, alternating).
 
 Comparators from another build of the library (LBF_LIB=<its liblbfhash.so>):
   --hash-only        h1, h4, h64 alone (a library without the text entry points)
@@ -42,7 +47,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from bitflood_amd import ChunkHasher, DeviceBuffer, new_states  # noqa: E402
+from bitflood_amd import ChunkHasher, DeviceBuffer, new_b64_states, new_states  # noqa: E402
 from bitflood_amd import hashing as H  # noqa: E402
 from bitflood_amd._capi import check, load  # noqa: E402
 
@@ -106,6 +111,8 @@ def main():
     ap.add_argument("--hash-only", action="store_true")
     ap.add_argument("--general-decode", action="store_true")
     ap.add_argument("--cases", default="", help="comma-separated subset of the cases (for a kernel trace of one)")
+    ap.add_argument("--share-chains", type=int, default=64, help="chains of the line-share sample")
+    ap.add_argument("--empty-reps", type=int, default=200, help="empty launches per round of the enqueue cost")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     n, cs = a.chains, a.chunk
@@ -155,7 +162,6 @@ def main():
                 b["hoff", p, k] = DeviceBuffer(8 * n)
                 b["hoff", p, k].upload(base * np.uint64(cs) + np.uint64(k * (cs // p)))
         if not a.hash_only:
-            from bitflood_amd import new_b64_states
             b["b64"].upload(new_b64_states(n))
             b["ooff"].upload(base * np.uint64(cs))
             b["caps"].upload(np.full(n, cs, dtype=np.uint32))
@@ -173,9 +179,15 @@ def main():
                     b["toff", p, k], b["tlen", p, k] = DeviceBuffer(8 * n), DeviceBuffer(4 * n)
                     b["toff", p, k].upload(base * np.uint64(slot) + np.uint64(cut[k]))
                     b["tlen", p, k].upload(np.full(n, cut[k + 1] - cut[k], dtype=np.uint32))
+            b["tlen0"] = DeviceBuffer(4 * n)
+            b["tlen0"].upload(np.zeros(n, dtype=np.uint32))
+        # a library from before the line path (LBF_LIB) has the general rule alone
+        routes = (("lines", True), ("scan", False)) if hasattr(lib, "lbf_set_b64_lines") else (("scan", None),)
 
-        def text_pieces(p):
+        def text_pieces(p, lines):
             def run():
+                if lines is not None:
+                    H.set_b64_lines(lines)
                 for k in range(p):
                     H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", p, k], b["tlen", p, k],
                                         b["fin1"] if k == p - 1 else b["fin0"], n, b["out"], b["ooff"], b["caps"],
@@ -191,10 +203,35 @@ def main():
                                     b["fin1"] if k == p - 1 else b["fin0"], n, b["dig"], b["ref"], b["ver"], stream=sp)
             return run
 
-        cases = [] if a.hash_only else [(f"t{p}", text_pieces(p), p) for p in parts]
+        def empty_launch(lines):
+            def run():
+                H.set_b64_lines(lines)
+                H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", 1, 0], b["tlen0"], b["fin0"], n,
+                                    b["out"], b["ooff"], b["caps"], b["osz"], b["dig"], b["ref"], b["ver"], b["poff"],
+                                    b["psz"], stream=sp)
+            return run
+
+        def line_share(p):
+            """The line path's share of the characters of case t<p>: the first chains through the batch call."""
+            m = min(a.share_chains, n)
+            text = b["text"].download(m * slot)
+            cut = [k * tl // p for k in range(p + 1)]
+            b64s, shas = new_b64_states(m), new_states(m)
+            out = np.zeros(m * cs, dtype=np.uint8)
+            H.set_b64_lines(True)
+            with ChunkHasher(device_mask=1) as h:
+                for k in range(p):
+                    h.update_text(b64s, shas, text, np.arange(m) * slot + cut[k], np.full(m, cut[k + 1] - cut[k]), out,
+                                  np.arange(m) * cs, np.full(m, cs), final=np.full(m, k == p - 1))
+                st = h.b64_update_stats()
+            assert st["line_chars"] + st["scan_chars"] == m * tl, st
+            return round(st["line_chars"] / (m * tl), 6)
+
+        cases = [] if a.hash_only else [(f"t{p}_{route}", text_pieces(p, on), p) for p in parts for route, on in routes]
         cases += [(f"h{p}", hash_pieces(p), p) for p in parts]
         if a.cases:
-            cases = [c for c in cases if c[0] in a.cases.split(",")]
+            want = a.cases.split(",")  # "t4" names both of its routes, "t4_lines" one
+            cases = [c for c in cases if c[0] in want or c[0].split("_")[0] in want]
         decoded_once = any(name.startswith("t") for name, _, _ in cases)  # the t cases come first
         probe = min(64 << 20, n * cs)  # the part of the decoded bytes that is compared with the chunks
         ms = {name: [] for name, _, _ in cases}
@@ -233,10 +270,28 @@ def main():
             med = statistics.median(ms[name])
             res["cases"][name] = {"launches_per_pass": launches, "ms_per_4gib_median": round(med * 4 / gib, 4),
                                   "ms_min": round(min(ms[name]) * 4 / gib, 4),
-                                  "ms_max": round(max(ms[name]) * 4 / gib, 4), "results_agree": agree[name]}
+                                  "ms_max": round(max(ms[name]) * 4 / gib, 4),
+                                  "spread_ms": round((max(ms[name]) - min(ms[name])) * 4 / gib, 4),
+                                  "results_agree": agree[name]}
         if not a.hash_only and not a.cases:
-            res["decode_share_ms"] = {f"t{p}": round(res["cases"][f"t{p}"]["ms_per_4gib_median"] -
-                                                     res["cases"][f"h{p}"]["ms_per_4gib_median"], 4) for p in parts}
+            res["decode_share_ms"] = {f"t{p}_{route}": round(res["cases"][f"t{p}_{route}"]["ms_per_4gib_median"] -
+                                                              res["cases"][f"h{p}"]["ms_per_4gib_median"], 4)
+                                      for p in parts for route, _ in routes}
+            if len(routes) == 2:
+                res["line_share_of_chars"] = {f"t{p}": line_share(p) for p in parts}
+                us = {"lines": [], "scan": []}
+                timed(empty_launch(True), 10)
+                timed(empty_launch(False), 10)
+                for _ in range(a.rounds):
+                    for route, on in routes:
+                        us[route].append(timed(empty_launch(on), a.empty_reps) * 1e3)
+                med = {r: statistics.median(v) for r, v in us.items()}
+                res["empty_launch_us"] = {
+                    "pieces": n, "lines_median": round(med["lines"], 3), "scan_median": round(med["scan"], 3),
+                    "lines_min_max": [round(min(us["lines"]), 3), round(max(us["lines"]), 3)],
+                    "scan_min_max": [round(min(us["scan"]), 3), round(max(us["scan"]), 3)],
+                    "extra_enqueue_us_per_call": round(med["lines"] - med["scan"], 3)}
+                H.set_b64_lines(True)
         return emit(res, all(agree.values()))
     finally:
         for buf in bufs.values():

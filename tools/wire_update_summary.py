@@ -24,7 +24,7 @@ import json
 import os
 import sys
 
-KERNELS = ("b64_update_kernel", "sha1_update_kernel", "b64_length_kernel", "b64_decode_kernel",
+KERNELS = ("b64_update_lines_kernel", "b64_update_kernel", "sha1_update_kernel", "b64_length_kernel", "b64_decode_kernel",
            "b64_decode_canon_kernel")
 LAUNCHES = {"t1": 1, "t4": 4, "t64": 64}
 
