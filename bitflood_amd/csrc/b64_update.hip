@@ -16,7 +16,9 @@
 // continues the encoder's layout is taken first by b64_update_lines.hip's
 // kernel (unless lbf_set_b64_lines switched it off), which moves the record on
 // and hands over, through the piece table's two arrays, where the chain stood
-// and how many characters it took; this kernel decodes what is left.
+// and how many characters it took; unbroken text in what that left is taken
+// next by b64_flat.hip's kernel (lbf_set_b64_flat), which hands over the same
+// two numbers; this kernel decodes what is left.
 //
 // A translation unit of its own, like sha1_update.hip: the shipped kernels'
 // ISA stays as recorded (tests/test_isa.py).  DESIGN.md §4.7.
@@ -26,6 +28,7 @@
 
 #include <atomic>
 
+#include "b64_flat.hpp"
 #include "b64_update_lines.hpp"
 #include "lbf_internal.hpp"
 
@@ -342,7 +345,8 @@ extern "C" int lbf_b64_update_launch(lbf_b64_state* d_b64_states, lbf_sha1_state
                                      uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, void* stream) {
   return lbf::b64_update_launch_counted(d_b64_states, d_sha_states, n_states, d_state_of, d_text, d_text_offsets,
                                         d_text_lens, d_final, n, d_out, d_out_offsets, d_caps, d_out_sizes, d_digests,
-                                        d_expected, d_verdicts, d_piece_offsets, d_piece_sizes, nullptr, stream);
+                                        d_expected, d_verdicts, d_piece_offsets, d_piece_sizes, nullptr, nullptr,
+                                        stream);
 }
 
 int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
@@ -351,7 +355,7 @@ int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* 
                                    const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
                                    uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                                    uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, uint32_t* d_line_chars,
-                                   void* stream) {
+                                   uint32_t* d_flat_chars, void* stream) {
   const std::string who = "lbf_b64_update_launch";
   if (n == 0) return LBF_OK;
   if (!d_b64_states || !d_sha_states || !d_text || !d_text_offsets || !d_text_lens || !d_out || !d_out_offsets ||
@@ -387,6 +391,7 @@ int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* 
   if (int rc = check_fits(d_piece_offsets, 8 * n, "lbf_b64_update_launch: piece_offsets")) return rc;
   if (int rc = check_fits(d_piece_sizes, 4 * n, "lbf_b64_update_launch: piece_sizes")) return rc;
   if (int rc = check_fits(d_line_chars, 4 * n, "lbf_b64_update_launch: line_chars")) return rc;
+  if (int rc = check_fits(d_flat_chars, 4 * n, "lbf_b64_update_launch: flat_chars")) return rc;
   lbf::B64UpdateParams p{};
   p.b64_states = reinterpret_cast<uint8_t*>(d_b64_states);
   p.n_states = n_states;
@@ -418,6 +423,24 @@ int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* 
     lp.taken = d_piece_sizes;
     lp.line_chars = d_line_chars;
     if (int rc = lbf::launch_b64_update_lines(lp, (uint32_t)n, st)) return rc;
+    p.lines = 1;
+  }
+  if (lbf::b64_flat_enabled()) {  // unbroken text in what is left: the same hand-over, from or behind the line path's
+    lbf::B64FlatParams fp{};
+    fp.b64_states = p.b64_states;
+    fp.n_states = n_states;
+    fp.state_of = d_state_of;
+    fp.text = p.text;
+    fp.text_off = d_text_offsets;
+    fp.text_len = d_text_lens;
+    fp.out = d_out;
+    fp.out_off = d_out_offsets;
+    fp.cap = d_caps;
+    fp.before = d_piece_offsets;
+    fp.taken = d_piece_sizes;
+    fp.flat_chars = d_flat_chars;
+    fp.after_lines = p.lines;
+    if (int rc = lbf::launch_b64_update_flat(fp, (uint32_t)n, st)) return rc;
     p.lines = 1;
   }
   hipLaunchKernelGGL(lbf::b64_update_kernel, dim3((uint32_t)n), dim3(lbf::kThreads), 0, st, p);

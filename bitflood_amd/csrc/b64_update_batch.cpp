@@ -5,10 +5,10 @@
 // on the device and how they come back is b64_update_plan.hpp; the text is cut
 // into launches and packed into copies by update_plan.hpp.  Here the plan meets
 // the stream: per launch one H2D per run of adjacent text pieces, one of the
-// touched state pairs and tables, lbf_b64_update_launch (with one more table:
-// the characters of each piece the line path took, for
-// lbf_ctx_b64_update_stats), the tables back, then only the bytes the launch
-// decoded.
+// touched state pairs and tables, lbf_b64_update_launch (with two more tables:
+// the characters of each piece the line path and the flat path took, for
+// lbf_ctx_b64_update_stats and lbf_ctx_b64_flat_stats), the tables back, then
+// only the bytes the launch decoded.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -73,10 +73,11 @@ int text_run_launch(lbf_ctx* ctx, hipStream_t st, const TextCall& c, const std::
   const uint64_t out_area = b64_update_places(decoded, ncarry, len, cap, places);
   // one block of tables, up and back: b64 states | SHA states | text offsets |
   // slot starts | piece offsets | text lengths | chunk sizes | piece sizes |
-  // decoded lengths | line-path characters | expected | digests | final flags | verdicts
+  // decoded lengths | line-path characters | flat-path characters | expected | digests | final flags | verdicts
   const uint64_t sha_at = 16 * m, toff_at = sha_at + 96 * m, slot_at = toff_at + 8 * m, poff_at = slot_at + 8 * m,
                  tlen_at = poff_at + 8 * m, cap_at = tlen_at + 4 * m, psize_at = cap_at + 4 * m,
-                 osize_at = psize_at + 4 * m, lines_at = osize_at + 4 * m, exp_at = lines_at + 4 * m,
+                 osize_at = psize_at + 4 * m, lines_at = osize_at + 4 * m, flat_at = lines_at + 4 * m,
+                 exp_at = flat_at + 4 * m,
                  dig_at = exp_at + 20 * m, fin_at = dig_at + 20 * m, ver_at = fin_at + m, tab_bytes = ver_at + m;
   std::vector<uint8_t> tab(tab_bytes, 0), bytes;
   SyncOnExit sync{st};  // after the vectors the copies use: every exit waits for the stream before they go
@@ -89,6 +90,7 @@ int text_run_launch(lbf_ctx* ctx, hipStream_t st, const TextCall& c, const std::
   const uint32_t* h_psize = reinterpret_cast<const uint32_t*>(tab.data() + psize_at);
   const uint32_t* h_osize = reinterpret_cast<const uint32_t*>(tab.data() + osize_at);
   const uint32_t* h_lines = reinterpret_cast<const uint32_t*>(tab.data() + lines_at);  // zero on the way up
+  const uint32_t* h_flat = reinterpret_cast<const uint32_t*>(tab.data() + flat_at);    // as well
   for (uint64_t k = 0; k < m; ++k) {
     const uint64_t i = cuts[k].piece, s = update_state_of(c.state_of, i);
     h_b64[k] = c.b64[s];
@@ -116,7 +118,8 @@ int text_run_launch(lbf_ctx* ctx, hipStream_t st, const TextCall& c, const std::
           reinterpret_cast<const uint64_t*>(d_tab + slot_at), reinterpret_cast<const uint32_t*>(d_tab + cap_at),
           reinterpret_cast<uint32_t*>(d_tab + osize_at), d_tab + dig_at, c.expected ? d_tab + exp_at : nullptr,
           c.expected ? d_tab + ver_at : nullptr, reinterpret_cast<uint64_t*>(d_tab + poff_at),
-          reinterpret_cast<uint32_t*>(d_tab + psize_at), reinterpret_cast<uint32_t*>(d_tab + lines_at), st))
+          reinterpret_cast<uint32_t*>(d_tab + psize_at), reinterpret_cast<uint32_t*>(d_tab + lines_at),
+          reinterpret_cast<uint32_t*>(d_tab + flat_at), st))
     return rc;
   LBF_HIP_TRY(hipMemcpyAsync(tab.data(), d_tab, tab.size(), hipMemcpyDeviceToHost, st));
   LBF_HIP_TRY(hipStreamSynchronize(st));
@@ -126,6 +129,7 @@ int text_run_launch(lbf_ctx* ctx, hipStream_t st, const TextCall& c, const std::
     const uint32_t by_lines = std::min(h_lines[k], len[k]);
     ctx->b64_line_chars += by_lines;
     ctx->b64_scan_chars += len[k] - by_lines;
+    ctx->b64_flat_chars += std::min(h_flat[k], len[k] - by_lines);  // a share of the scan path's count
     got[k] = h_psize[k];
     dev_at[k] = places[k].dev;
     total += got[k];

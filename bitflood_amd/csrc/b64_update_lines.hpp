@@ -38,14 +38,15 @@ int launch_b64_update_lines(const B64LinesParams& p, uint32_t n, hipStream_t str
 constexpr bool kB64LinesDefault = true;
 bool b64_lines_enabled();
 
-// lbf_b64_update_launch with one more device array (null, or n entries, zero
-// on entry): the characters of each piece that went through the line path.
+// lbf_b64_update_launch with two more device arrays (each null, or n entries,
+// zero on entry): the characters of each piece that went through the line
+// path, and those the flat path (b64_flat.hip) took of what it left.
 int b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
                               const uint32_t* d_state_of, const char* d_text, const uint64_t* d_text_offsets,
                               const uint32_t* d_text_lens, const uint8_t* d_final, uint64_t n, uint8_t* d_out,
                               const uint64_t* d_out_offsets, const uint32_t* d_caps, uint32_t* d_out_sizes,
                               uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                               uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, uint32_t* d_line_chars,
-                              void* stream);
+                              uint32_t* d_flat_chars, void* stream);
 
 }  // namespace lbf

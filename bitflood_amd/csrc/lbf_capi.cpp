@@ -256,6 +256,14 @@ extern "C" int lbf_ctx_b64_update_stats(lbf_ctx* ctx, uint64_t* line_chars, uint
   return LBF_OK;
 }
 
+extern "C" int lbf_ctx_b64_flat_stats(lbf_ctx* ctx, uint64_t* flat_chunks, uint64_t* flat_chars) {
+  if (!ctx) return fail(LBF_ERR_INVALID, "null context");
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  if (flat_chunks) *flat_chunks = ctx->b64_flat_chunks;
+  if (flat_chars) *flat_chars = ctx->b64_flat_chars;
+  return LBF_OK;
+}
+
 extern "C" int lbf_ctx_staging_stats(lbf_ctx* ctx, uint64_t* staged_bytes, uint64_t* direct_bytes) {
   if (!ctx) return fail(LBF_ERR_INVALID, "null context");
   std::lock_guard<std::mutex> lock(ctx->mu);  // between jobs

@@ -242,5 +242,8 @@ struct lbf_ctx {
   uint64_t update_bytes = 256ull << 20;
   // lbf_b64_update_batch's characters by decode path (lbf_ctx_b64_update_stats), guarded by mu
   uint64_t b64_line_chars = 0, b64_scan_chars = 0;
+  // the flat path's share of the two above (lbf_ctx_b64_flat_stats), guarded by mu: b64_general's chunks the
+  // flat pass decoded, b64_scan_chars' characters the flat kernel took
+  uint64_t b64_flat_chunks = 0, b64_flat_chars = 0;
   mutable std::mutex mu;
 };

@@ -60,6 +60,10 @@ struct B64Launch {
   uint32_t max_cap;
 };
 int launch_b64_decode(const B64Launch& b, hipStream_t stream);
+// Its two halves, for a caller that puts another pass between them (wire_batch.cpp: the flat pass of b64_flat.hip
+// marks redo[] too): the one-pass decode of the first b.n chunks, the general decode of those redo[] names.
+int launch_b64_decode_one_pass(const B64Launch& b, hipStream_t stream);
+int launch_b64_decode_general(const B64Launch& b, hipStream_t stream);
 // Device base64 encode (kern_b64.hpp): n chunks' bytes -> their SendChunk text.
 // max_size: the largest chunk (sets the tiles per chunk).
 int launch_b64_encode(const uint8_t* data, const uint64_t* data_off, const uint32_t* size, uint8_t* text,

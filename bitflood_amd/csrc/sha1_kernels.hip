@@ -190,23 +190,30 @@ static int b64_tiled_launch(uint32_t n, uint32_t tiles, F launch) {
   return LBF_OK;
 }
 
-int launch_b64_decode(const B64Launch& b, hipStream_t stream) {
+int launch_b64_decode_one_pass(const B64Launch& b, hipStream_t stream) {
   if (b.n == 0) return LBF_OK;
   // the one-pass decode of canonically laid-out text, tile by tile (each
-  // chunk's tiles cover its text and its output slot); then the general
-  // two-pass decode of whatever it handed back (a workgroup per chunk, most
-  // exit at once)
+  // chunk's tiles cover its text and its output slot)
   const uint32_t tiles = std::max<uint32_t>(
       1u, std::max((b.max_text_len + kDecText - 1) / kDecText, (b.max_cap + kDecBytes - 1) / kDecBytes));
-  if (int rc = b64_tiled_launch(b.n, (tiles + kDecTilesPerGroup - 1) / kDecTilesPerGroup, [&](dim3 grid, uint32_t c0) {
-        hipLaunchKernelGGL(b64_decode_canon_kernel, grid, dim3(kB64Threads), 0, stream, b.text, b.text_off, b.text_len,
-                           b.out, b.out_off, b.cap, b.sizes, b.over, b.redo, tiles, c0);
-      }))
-    return rc;
+  return b64_tiled_launch(b.n, (tiles + kDecTilesPerGroup - 1) / kDecTilesPerGroup, [&](dim3 grid, uint32_t c0) {
+    hipLaunchKernelGGL(b64_decode_canon_kernel, grid, dim3(kB64Threads), 0, stream, b.text, b.text_off, b.text_len,
+                       b.out, b.out_off, b.cap, b.sizes, b.over, b.redo, tiles, c0);
+  });
+}
+
+int launch_b64_decode_general(const B64Launch& b, hipStream_t stream) {
+  if (b.n == 0) return LBF_OK;
+  // the general two-pass decode of whatever redo[] names (a workgroup per chunk, most exit at once)
   hipLaunchKernelGGL(b64_decode_kernel, dim3(b.n), dim3(kB64Threads), 0, stream, b.text, b.scratch, b.text_off,
                      b.sext_off, b.text_len, b.out, b.out_off, b.cap, b.sizes, b.over, (const uint8_t*)b.redo);
   LBF_HIP_TRY(hipGetLastError());
   return LBF_OK;
+}
+
+int launch_b64_decode(const B64Launch& b, hipStream_t stream) {
+  if (int rc = launch_b64_decode_one_pass(b, stream)) return rc;
+  return launch_b64_decode_general(b, stream);
 }
 
 int launch_b64_encode(const uint8_t* data, const uint64_t* data_off, const uint32_t* size, uint8_t* text,

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 
+#include "b64_flat.hpp"
 #include "lbf_host.hpp"
 
 using namespace lbf;
@@ -135,8 +136,14 @@ struct B64Verify {
   uint32_t* out_sizes;
   uint8_t* verdicts;
   uint64_t tlo = UINT64_MAX, thi = 0, olo = UINT64_MAX, ohi = 0;  // the spans of the text and of the output slots
-  uint32_t max_tlen = 0, max_cap = 0;
+  uint32_t max_tlen = 0, max_cap = 0;  // of the chunks the one-pass decode gets
   std::vector<SlotRun> runs;  // the output slots the D2H writes, and nothing between them
+  // The chunks' order on the device: order[k] = the caller's index of device chunk k.  The first n_canon go
+  // through the one-pass decode; the rest are the flat pass's candidates (b64_flat.hpp), which skip it -- their
+  // text would fail it at the first separator place.  With the flat path off: the caller's order, n_canon = n.
+  std::vector<uint32_t> order;
+  uint64_t n_canon = 0;
+  uint32_t flat_tlen = 0;  // the candidates' longest text
   // bytes per chunk of the inputs (offsets, lengths, caps, expected) and of the results (sizes, over,
   // verdicts, redo flags); kIn * n keeps 4-byte alignment
   static constexpr uint64_t kIn = 8 * 3 + 4 * 2 + 20, kRes = 4 + 1 + 1 + 1;
@@ -165,10 +172,21 @@ int b64_verify_check(B64Verify& v, uint64_t text_len, uint64_t out_len) {
     std::vector<uint64_t> olens(v.expected_sizes, v.expected_sizes + n);
     if (int rc = checked_slot_runs(v.out_offsets, olens.data(), n, "lbf_b64_verify_batch", v.runs)) return rc;
   }
+  const bool flat = b64_flat_enabled();
+  v.order.reserve(n);
+  std::vector<uint32_t> candidates;
   for (uint64_t i = 0; i < n; ++i) {
+    if (flat && b64_flat_candidate(v.text_lens[i], v.expected_sizes[i])) {
+      candidates.push_back((uint32_t)i);
+      v.flat_tlen = std::max(v.flat_tlen, v.text_lens[i]);
+      continue;
+    }
+    v.order.push_back((uint32_t)i);
     v.max_tlen = std::max(v.max_tlen, v.text_lens[i]);
     v.max_cap = std::max(v.max_cap, v.expected_sizes[i]);
   }
+  v.n_canon = v.order.size();
+  v.order.insert(v.order.end(), candidates.begin(), candidates.end());
   v.tlo &= ~15ull;
   if (v.out) v.olo &= ~15ull;
   return LBF_OK;
@@ -182,16 +200,19 @@ std::vector<uint8_t> b64_verify_tables(const B64Verify& v, uint64_t& sext, uint6
   std::vector<uint64_t> toff(n), soff(n), ooff(n);
   std::vector<uint32_t> tlen(n), cap(n);
   sext = 0, outb = 0;
-  for (uint64_t i = 0; i < n; ++i) {
-    toff[i] = v.text_offsets[i] - v.tlo;
-    soff[i] = sext;
+  std::vector<uint8_t> exp(20 * n);
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint64_t i = v.order[k];
+    toff[k] = v.text_offsets[i] - v.tlo;
+    soff[k] = sext;
     sext += up(v.text_lens[i], 16);
-    tlen[i] = v.text_lens[i];
-    cap[i] = v.expected_sizes[i];
+    tlen[k] = v.text_lens[i];
+    cap[k] = v.expected_sizes[i];
+    memcpy(exp.data() + 20 * k, v.expected + 20 * i, 20);
     if (v.out) {
-      ooff[i] = v.out_offsets[i] - v.olo;
+      ooff[k] = v.out_offsets[i] - v.olo;
     } else {
-      ooff[i] = outb;
+      ooff[k] = outb;
       outb += up(v.expected_sizes[i], 16);
     }
   }
@@ -207,27 +228,33 @@ std::vector<uint8_t> b64_verify_tables(const B64Verify& v, uint64_t& sext, uint6
   put(ooff.data(), 8 * n);
   put(tlen.data(), 4 * n);
   put(cap.data(), 4 * n);
-  put(v.expected, 20 * n);
+  put(exp.data(), 20 * n);
   return in;
 }
 
-// The results of one call (sizes, over, verdicts, redo flags per chunk) as the
-// caller's verdicts and sizes, and the context's decode-path counters.
+// The results of one call (sizes, over, verdicts, redo flags per chunk, in the
+// device's order) as the caller's verdicts and sizes, and the context's
+// decode-path counters.  A candidate of the flat pass is "not the encoder's
+// layout" whichever kernel decoded it: general_chunks counts it, and
+// flat_chunks those of them the flat pass kept.
 void b64_verify_results(lbf_ctx* ctx, const B64Verify& v, const std::vector<uint8_t>& res) {
   const uint64_t n = v.n;
   const uint8_t* redo = res.data() + 6 * n;
-  uint64_t general = 0;
-  for (uint64_t i = 0; i < n; ++i) general += redo[i] != 0;
+  uint64_t general = n - v.n_canon, flat = 0;
+  for (uint64_t k = 0; k < v.n_canon; ++k) general += redo[k] != 0;
+  for (uint64_t k = v.n_canon; k < n; ++k) flat += redo[k] == 0;
   ctx->b64_general += general;
   ctx->b64_one_pass += n - general;
+  ctx->b64_flat_chunks += flat;
   const uint32_t* sizes = reinterpret_cast<const uint32_t*>(res.data());
   const uint8_t* over = res.data() + 4 * n;
   const uint8_t* ver = over + n;
-  for (uint64_t i = 0; i < n; ++i) {
+  for (uint64_t k = 0; k < n; ++k) {
+    const uint64_t i = v.order[k];
     // ChunkMethods.cpp:156: the decoded length must be the chunk's size
-    const bool longer = over[i] != 0;
-    v.verdicts[i] = (ver[i] && !longer && sizes[i] == v.expected_sizes[i]) ? 1 : 0;
-    if (v.out_sizes) v.out_sizes[i] = longer ? v.expected_sizes[i] + 1 : sizes[i];
+    const bool longer = over[k] != 0;
+    v.verdicts[i] = (ver[k] && !longer && sizes[k] == v.expected_sizes[i]) ? 1 : 0;
+    if (v.out_sizes) v.out_sizes[i] = longer ? v.expected_sizes[i] + 1 : sizes[k];
   }
 }
 
@@ -266,7 +293,17 @@ int b64_verify_run(lbf_ctx* ctx, const B64Verify& v) {
   uint8_t* d_redo = d_ver + n;  // uploaded as zeros
   lbf::B64Launch b{d_text, d_sext, d_toff, d_soff, d_tlen, d_out,   d_ooff, d_cap,
                    d_sizes, d_over, d_redo, (uint32_t)n, v.max_tlen, v.max_cap};
-  if (int rc = lbf::launch_b64_decode(b, st)) return rc;
+  // the one-pass decode of the first n_canon chunks, the flat pass of the candidates behind them, then the
+  // general decode of whatever either handed back
+  lbf::B64Launch canon = b;
+  canon.n = (uint32_t)v.n_canon;
+  if (int rc = lbf::launch_b64_decode_one_pass(canon, st)) return rc;
+  if (v.n_canon < n) {
+    const lbf::B64FlatDecode f{d_text, d_toff, d_tlen, d_out, d_ooff, d_cap, d_sizes, d_over, d_redo,
+                               (uint32_t)v.n_canon, (uint32_t)(n - v.n_canon), v.flat_tlen};
+    if (int rc = lbf::launch_b64_flat_decode(f, st)) return rc;
+  }
+  if (int rc = lbf::launch_b64_decode_general(b, st)) return rc;
   // the decoded lengths are the chunk sizes the hash kernels read
   if (int rc = lbf_sha1_launch(d_out, d_ooff, d_sizes, n, nullptr, d_exp, d_ver, st)) return rc;
   LBF_HIP_TRY(hipMemcpyAsync(res.data(), d_res, res.size(), hipMemcpyDeviceToHost, st));

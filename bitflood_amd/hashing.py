@@ -157,6 +157,15 @@ class ChunkHasher:
         check(self._lib.lbf_ctx_b64_update_stats(self._h, ctypes.byref(line), ctypes.byref(scan)))
         return {"line_chars": line.value, "scan_chars": scan.value}
 
+    def b64_flat_stats(self) -> dict:
+        """The flat path's share of the two counters above: verify_b64's chunks
+        of unbroken text that the flat pass decoded (counted in "general" too)
+        and update_text's characters that the flat kernel took (counted in
+        "scan_chars" too) (lbf_ctx_b64_flat_stats)."""
+        chunks, chars = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(self._lib.lbf_ctx_b64_flat_stats(self._h, ctypes.byref(chunks), ctypes.byref(chars)))
+        return {"flat_chunks": chunks.value, "flat_chars": chars.value}
+
     # -- caller-pinned sources (lbf_host_register) ---------------------------
     def register_host(self, data) -> None:
         """Pin `data` (a contiguous numpy array / buffer) for this context:
@@ -533,6 +542,13 @@ def set_b64_lines(on) -> bool:
     return bool(load().lbf_set_b64_lines(1 if on else 0))
 
 
+def set_b64_flat(on) -> bool:
+    """lbf_set_b64_flat: the flat path (unbroken base64 text, as bitflood's Java
+    and Perl peers send it) of verify_b64 / update_text / b64_update_launch on
+    or off, process-wide; returns the previous setting."""
+    return bool(load().lbf_set_b64_flat(1 if on else 0))
+
+
 def synchronize():
     check(load().lbf_device_synchronize())
 
@@ -543,5 +559,5 @@ def set_kernel_variant(v: int):
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
-           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "set_b64_flat", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

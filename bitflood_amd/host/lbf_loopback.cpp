@@ -23,6 +23,10 @@
 //    which bounds the verify latency the batching adds.
 // With --corrupt K the seeder flips one byte of every K-th chunk AFTER its own
 // verify (a wire error); the leecher must reject it and ask again.
+// With --wire-layout flat the seeder frames every chunk as unbroken base64, as
+// bitflood's Java and Perl peers do (a host-side encode; the default, xmlrpc,
+// is xmlrpc++'s 73-character lines).  The leecher takes either; its line
+// reports the chunks its flat pass decoded (LBF_B64_FLAT=1 switches that on).
 // With --synthetic the seeder holds no file: its chunk bytes come from the
 // counter-mode generator (the stream lbf_fill_synthetic writes), re-verified on
 // the GPU against the flood file before sending (Flood::VerifyChunks, the verify
@@ -97,6 +101,8 @@ struct Opts {
   bool seeder_pipeline = false;  // --pipelined-seeder: verify batch k+1 while batch k is encoded
   bool gpu_decode = true;        // the leecher's base64 decode on the GPU with its verify (--cpu-decode: on the host)
   bool gpu_encode = false;       // --gpu-encode: the seeder's base64 encode on the GPU with its verify (--synthetic)
+  bool wire_flat = false;        // --wire-layout flat: the seeder frames chunks as unbroken base64, as a Java or Perl
+                                 // seeder would (a host-side encode; the default, xmlrpc, is xmlrpc++'s lines)
   unsigned seeder_workers = 1;   // --seeder-workers S: the seeder's verify/encode workers (each its own context)
   enum Role { BOTH, SEEDER, LEECHER } role = BOTH;  // --role: both peers in this process, or one of them
   int port = -1;                 // seeder: port to listen on (0 / unset = any); leecher: port to dial
@@ -394,6 +400,38 @@ bool files_equal(const std::string& a, const std::string& b) {
 }
 
 // ---- seeder ------------------------------------------------------------------
+// --wire-layout flat: a chunk's base64 as bitflood's Java and Perl peers write it
+// (Base64.encodeToString(arg, false); encode_base64($value, '')): RFC 4648, no
+// line separators.
+std::string flat_base64(const U8* d, size_t n) {
+  static const char kAlpha[] = "ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz0123456789+/";
+  std::string s;
+  s.resize(4 * ((n + 2) / 3));
+  char* o = &s[0];
+  size_t i = 0;
+  for (; i + 3 <= n; i += 3) {
+    const U32 x = (U32)d[i] << 16 | (U32)d[i + 1] << 8 | d[i + 2];
+    *o++ = kAlpha[x >> 18];
+    *o++ = kAlpha[(x >> 12) & 63];
+    *o++ = kAlpha[(x >> 6) & 63];
+    *o++ = kAlpha[x & 63];
+  }
+  if (n - i == 1) {
+    const U32 x = (U32)d[i] << 16;
+    *o++ = kAlpha[x >> 18];
+    *o++ = kAlpha[(x >> 12) & 63];
+    *o++ = '=';
+    *o++ = '=';
+  } else if (n - i == 2) {
+    const U32 x = (U32)d[i] << 16 | (U32)d[i + 1] << 8;
+    *o++ = kAlpha[x >> 18];
+    *o++ = kAlpha[(x >> 12) & 63];
+    *o++ = kAlpha[(x >> 6) & 63];
+    *o++ = '=';
+  }
+  return s;
+}
+
 struct SeederStats {
   U64 requests = 0, sent = 0, refused = 0, corrupted = 0;
   double verify_s = 0, encode_s = 0;
@@ -572,6 +610,11 @@ void seeder_main(int lfd, FloodFileSPtr ff, std::string root, const Opts& o, See
           tmp[sizes[k] / 2] ^= 0x01;
           data = tmp.data();
         }
+        if (o.wire_flat) {
+          const std::string t = flat_base64(data, sizes[k]);
+          out[k] = PeerWire::FrameSendChunkText(keys[k].first, keys[k].second, t.data(), t.size());
+          return;
+        }
         out[k] = PeerWire::EncodeSendChunk(keys[k].first, keys[k].second, data, sizes[k]);
       });
       mine.encode_s += secs(t1, Clock::now());
@@ -711,6 +754,12 @@ int main(int argc, char** argv) {
     else if (a == "--seeder-workers") o.seeder_workers = (unsigned)strtoul(val(), nullptr, 10);
     else if (a == "--gpu-encode") o.gpu_encode = true;
     else if (a == "--cpu-encode") o.gpu_encode = false;
+    else if (a == "--wire-layout") {
+      const std::string v = val();
+      if (v == "flat") o.wire_flat = true;
+      else if (v == "xmlrpc") o.wire_flat = false;
+      else die("--wire-layout takes xmlrpc or flat");
+    }
     else if (a == "--role") {
       const std::string r = val();
       if (r == "both") o.role = Opts::BOTH;
@@ -729,7 +778,7 @@ int main(int argc, char** argv) {
               "                    [--threads T]\n"
               "                    [--corrupt K] [--dir DIR] [--keep] [--synthetic] [--no-register]\n"
               "                    [--verifiers V] [--pipelined-seeder] [--gpu-decode | --cpu-decode]\n"
-              "                    [--gpu-encode | --cpu-encode] [--seeder-workers S]\n"
+              "                    [--gpu-encode | --cpu-encode] [--wire-layout xmlrpc|flat] [--seeder-workers S]\n"
               "                    [--role both | --role seeder [--port P] [--port-file F] |\n"
               "                     --role leecher --port P]   (seeder and leecher: same --dir and options)\n");
       return 2;
@@ -738,6 +787,7 @@ int main(int argc, char** argv) {
   if (o.chunksize == 0 || o.window == 0 || o.batch == 0) die("chunksize, window and batch must be > 0");
   if (o.verifiers == 0 || o.verifiers > 8) die("verifiers must be 1..8");
   if (o.seeder_workers == 0 || o.seeder_workers > 8) die("seeder workers must be 1..8");
+  if (o.gpu_encode && o.wire_flat) die("--wire-layout flat is a host-side encode: not with --gpu-encode");
   if (o.gpu_encode && !o.synthetic) die("--gpu-encode needs --synthetic (the file seeder reads and verifies in one call)");
   if (o.role != Opts::BOTH && o.dir.empty()) die("--role seeder/leecher needs --dir (the directory both peers share)");
   if (o.role == Opts::LEECHER && (o.port <= 0 || o.port > 65535)) die("--role leecher needs --port");
@@ -1121,6 +1171,11 @@ int main(int argc, char** argv) {
       for (const std::vector<Arena>* set : {&arenas, &texts})
         for (const Arena& a : *set) (void)lbf_host_unregister(c, a.data());
   vfl.clear();
+  U64 flat_chunks = 0;  // the chunks the verifiers' contexts decoded through the flat pass (lbf_set_b64_flat)
+  for (lbf_ctx* c : vctx) {
+    uint64_t chunks = 0;
+    if (lbf_ctx_b64_flat_stats(c, &chunks, nullptr) == LBF_OK) flat_chunks += chunks;
+  }
   for (unsigned v = 1; v < o.verifiers; ++v) lbf_ctx_destroy(vctx[v]);
   free(arena_mem);
   free(text_mem);
@@ -1160,12 +1215,12 @@ int main(int argc, char** argv) {
   printf("{\"config\": \"C5 loopback 2-peer\", \"role\": \"%s\", \"pid\": %d, \"bytes\": %llu, \"chunk_size\": %u, "
          "\"chunks\": %zu, "
          "\"window\": %u, \"batch\": %u, \"deadline_ms\": %u, \"verifiers\": %u, \"seeder_pipelined\": %s, "
-         "\"gpu_decode\": %s, \"gpu_encode\": %s, \"seeder_workers\": %u, "
+         "\"gpu_decode\": %s, \"gpu_encode\": %s, \"wire_layout\": \"%s\", \"seeder_workers\": %u, "
          "\"threads\": %u, \"seconds\": %.3f, \"payload_gibs\": %.3f, "
          "\"wire_gibs\": %.3f, \"encode_flood_s\": %.3f, "
          "\"leecher\": {\"batches\": %zu, \"mean_batch\": %.1f, \"decode_s\": %.3f, \"verify_s\": %.3f, "
          "\"write_s\": %.3f, "
-         "\"rejected\": %zu, \"undecodable\": %zu}, \"seeder\": %s, "
+         "\"rejected\": %zu, \"undecodable\": %zu, \"flat_chunks\": %llu}, \"seeder\": %s, "
          "\"verify_latency_us\": {\"p50\": %.0f, \"p90\": %.0f, \"p99\": %.0f, \"max\": %.0f}, "
          "\"accept_latency_us\": {\"p50\": %.0f, \"p90\": %.0f, \"p99\": %.0f, \"max\": %.0f}, "
          "\"resume_verify_complete\": %s, \"files_identical\": %s, \"corrupt_every\": %u, \"corrupted_sent\": %s, "
@@ -1173,10 +1228,10 @@ int main(int argc, char** argv) {
          o.role == Opts::BOTH ? "both" : "leecher", (int)getpid(), (unsigned long long)o.size, o.chunksize, total,
          o.window, o.batch, o.deadline_ms, o.verifiers,
          o.seeder_pipeline ? "true" : "false", o.gpu_decode ? "true" : "false",
-         o.gpu_encode ? "true" : "false", o.seeder_workers, o.threads, wall,
+         o.gpu_encode ? "true" : "false", o.wire_flat ? "flat" : "xmlrpc", o.seeder_workers, o.threads, wall,
          payload / wall / (1u << 30), wire_bytes / wall / (1u << 30), encode_s, batches,
          batches ? (double)(accepted + rejected) / batches : 0.0, decode_s, verify_s, write_s, rejected, undecodable,
-         seeder_json, pct(0.5), pct(0.9), pct(0.99), lat_us.empty() ? 0.0 : lat_us.back(), pct_of(acc_us, 0.5),
+         (unsigned long long)flat_chunks, seeder_json, pct(0.5), pct(0.9), pct(0.99), lat_us.empty() ? 0.0 : lat_us.back(), pct_of(acc_us, 0.5),
          pct_of(acc_us, 0.9), pct_of(acc_us, 0.99), acc_us.empty() ? 0.0 : acc_us.back(), resumed ? "true" : "false",
          same ? "true" : "false", o.corrupt, corrupted_json,
          o.synthetic ? "synthetic stream (generated on request, no seeder file)" : "file",

@@ -173,8 +173,15 @@ int lbf_files_ranges(lbf_ctx* ctx, const char* const* paths, uint32_t n_files, c
  * refused (LBF_ERR_INVALID).  Synchronous, on the context's first device.
  * Text and output in memory registered with lbf_host_register move by DMA
  * without staging.  lbf_ctx_b64_stats counts the chunks whose text had the
- * encoder's own layout (decoded in one pass) and the others (decoded by the
- * general two-pass kernel).  A chunk of more than 1 GiB (expected_sizes) or
+ * encoder's own layout (decoded in one pass) and the others.  Of the others,
+ * a chunk of more than 54 bytes whose text is its unbroken RFC 4648 text --
+ * text_lens[i] == 4 * ceil(expected_sizes[i] / 3) and not
+ * lbf_b64_put_length(expected_sizes[i]); what bitflood's Java and Perl peers
+ * send -- goes through the flat pass (one pass, no separator places;
+ * lbf_set_b64_flat, lbf_ctx_b64_flat_stats) and skips the encoder-layout
+ * attempt; the rest, and a candidate that holds anything but alphabet
+ * characters and a last group "xx==" / "xxx=", are decoded by the general
+ * two-pass kernel.  A chunk of more than 1 GiB (expected_sizes) or
  * 1.5 GiB of text is refused (LBF_ERR_INVALID): the kernels keep positions
  * within a chunk in 32 bits. */
 int lbf_b64_verify_batch(lbf_ctx* ctx, const char* text, uint64_t text_len, const uint64_t* text_offsets,
@@ -198,7 +205,9 @@ int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data
                                 const uint32_t* sizes, uint64_t n, const uint8_t* expected, uint8_t* verdicts,
                                 char* text, uint64_t text_len, const uint64_t* text_offsets);
 /* Chunks of lbf_b64_verify_batch calls on this context so far, by decode
- * path (diagnostics; either pointer may be NULL). */
+ * path (diagnostics; either pointer may be NULL).  general_chunks reads "not
+ * the encoder's layout": it counts the flat pass's candidates too, whichever
+ * kernel decoded them (lbf_ctx_b64_flat_stats has their share). */
 int lbf_ctx_b64_stats(lbf_ctx* ctx, uint64_t* one_pass_chunks, uint64_t* general_chunks);
 /* Length of that text for a chunk of `size` bytes (xmlrpc++'s encoder). */
 uint64_t lbf_b64_put_length(uint64_t size);
@@ -318,8 +327,8 @@ typedef struct lbf_b64_state {
 void lbf_b64_state_init(lbf_b64_state* states, uint64_t n);
 
 /* Device-resident and asynchronous on `stream`: four enqueues (three with the
- * line path off, lbf_set_b64_lines), no host round trip, no device
- * allocation.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
+ * line path off, lbf_set_b64_lines) and one more with the flat path on
+ * (lbf_set_b64_flat), no host round trip, no device allocation.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
  * continues chain d_state_of[i] (chain i when d_state_of is NULL): the pair
  * d_b64_states[s], d_sha_states[s] of n_states pairs (both arrays 16-byte
  * aligned).  Its chunk's slot is d_out[d_out_offsets[i], + d_caps[i]) -- the
@@ -333,9 +342,14 @@ void lbf_b64_state_init(lbf_b64_state* states, uint64_t n);
  * alphabet characters, a separator after every 18th -- is decoded from its
  * known places through tiles of whole lines, each tile validated before it is
  * stored; the record moves on in place and the work arrays carry the count to
- * the next kernel.  That kernel decodes the rest of every piece by the general
- * rule (one workgroup per piece) and fills the work arrays d_piece_offsets / d_piece_sizes (n
- * entries each, the caller's) with where each piece's new bytes lie;
+ * the next kernel.  The flat path, when switched on, follows (one workgroup
+ * per piece; with the line path off it goes first): of what is left it takes
+ * the prefix that is unbroken text -- the carried group completed, then whole
+ * groups of alphabet characters up to one that holds '=' -- through tiles of
+ * 5,184 characters, validated and handed on in the same way.  The last decode
+ * kernel takes the rest of every piece by the general rule (one workgroup per
+ * piece) and fills the work arrays d_piece_offsets / d_piece_sizes (n entries
+ * each, the caller's) with where each piece's new bytes lie;
  * lbf_sha1_update_launch absorbs exactly those; a last kernel clears the
  * verdict of a final piece whose decoded length is not d_caps[i].  A piece
  * with d_final[i] != 0 ends its chain: an unfinished group is dropped,
@@ -371,6 +385,22 @@ int lbf_set_b64_lines(int on);
  * text_lens of every accepted call.  The text of a chain that has ended counts
  * as scan_chars. */
 int lbf_ctx_b64_update_stats(lbf_ctx* ctx, uint64_t* line_chars, uint64_t* scan_chars);
+/* The flat path of lbf_b64_verify_batch, lbf_b64_update_launch and
+ * lbf_b64_update_batch, process-wide, as lbf_set_b64_lines: 0 switches it off
+ * (the enqueues and the routing are exactly those without it), anything else
+ * on.  Returns the previous value.  Until the first use or call of this
+ * function the value is LBF_B64_FLAT's (default off; "1" = on: the extra
+ * enqueue costs text in the encoder's layout more than a run's spread, so a
+ * receiver with Java or Perl peers switches it on).  Bytes,
+ * records, lengths and verdicts are the same either way. */
+int lbf_set_b64_flat(int on);
+/* The flat path's share of the two counters above (diagnostics; either pointer
+ * may be NULL).  flat_chunks: the chunks of lbf_b64_verify_batch calls that the
+ * flat pass decoded -- a sub-count of lbf_ctx_b64_stats' general_chunks.
+ * flat_chars: the characters of lbf_b64_update_batch calls that the flat kernel
+ * took -- a sub-count of lbf_ctx_b64_update_stats' scan_chars, which keeps
+ * counting every character the line path did not take. */
+int lbf_ctx_b64_flat_stats(lbf_ctx* ctx, uint64_t* flat_chunks, uint64_t* flat_chars);
 /* The same over host memory, synchronous on the context's first device.  Piece
  * i = text[text_offsets[i], + text_lens[i]) of chain state_of[i], whose chunk
  * is expected_sizes[i] bytes and lives at out[out_offsets[i], +

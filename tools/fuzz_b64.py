@@ -2,7 +2,9 @@
 """Randomised fuzz of the wire-form entry points (diagnostic, not a test).
 
 Each case is a batch of 1-64 chunks of 0 B to 300 KiB.  The texts are the
-encoder's (tests/test_gpu_b64.py xmlrpc_text, base64.h:154-210) or that text
+encoder's (tests/test_gpu_b64.py xmlrpc_text, base64.h:154-210), in a third of
+the cases the unbroken text a Java or Perl peer sends (base64.b64encode: the
+flat pass's candidates) and in a third a mix of the two, or such a text
 perturbed in one of the ways the parity test uses: junk or '=' inserted,
 characters dropped, truncation, an alphabet character flipped, '=' / junk /
 an alphabet character in place of a group character or a separator -- so both
@@ -15,6 +17,7 @@ first mismatch and prints the case seed (--seed S --cases 1 replays it).
 Usage: python tools/fuzz_b64.py [--seconds 90] [--seed 1]
 """
 import argparse
+import base64
 import hashlib
 import json
 import os
@@ -67,7 +70,11 @@ def one_case(h, seed):
     big = rng.random() < 0.2
     sizes = [int(rng.integers(0, 300 * 1024 if big and k % 8 == 0 else 4096)) for k in range(n)]
     datas = [rng.integers(0, 256, s, dtype=np.uint8).tobytes() for s in sizes]
-    texts, kinds = zip(*[perturb(rng, xmlrpc_text(d)) for d in datas])
+    # the layouts come from a generator of their own: a seed's chunks and damage are what they were without them
+    lrng = np.random.default_rng([seed, 1])
+    mode = int(lrng.integers(0, 3))  # all in the encoder's layout, all unbroken, mixed
+    flat = [mode == 1 or (mode == 2 and lrng.random() < 0.5) for _ in range(n)]
+    texts, kinds = zip(*[perturb(rng, base64.b64encode(d) if f else xmlrpc_text(d)) for d, f in zip(datas, flat)])
     align = int(rng.choice([1, 4, 16]))
     toffs, pos, buf = [], int(rng.integers(0, 16)), bytearray()
     buf += b"\0" * pos
@@ -93,7 +100,7 @@ def one_case(h, seed):
         want_len = len(w) if len(w) <= cap else cap + 1
         got = out[int(ooff[k]):int(ooff[k]) + min(len(w), cap)].tobytes()
         if int(dec[k]) != want_len or got != w[:cap] or bool(ver[k]) != (w == datas[k]):
-            return {"chunk": k, "kind": kinds[k], "size": cap, "text_len": len(texts[k]), "got_len": int(dec[k]),
+            return {"chunk": k, "kind": kinds[k], "layout": "flat" if flat[k] else "xmlrpc", "size": cap, "text_len": len(texts[k]), "got_len": int(dec[k]),
                     "want_len": want_len, "verdict": bool(ver[k])}
     # the sender's side over the same chunks (a few expected digests wrong)
     bad = rng.random(n) < 0.1

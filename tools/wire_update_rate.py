@@ -4,12 +4,18 @@
 in DESIGN.md §4.7 and §5, not gated).
 
 C2's shape: 16,384 chunks of 256 KiB (lbf_fill_synthetic) as the text
-xmlrpc++'s encoder writes for them (354,382 characters a chunk, built on the
-host slice by slice and uploaded).  One process alternates, round by round,
-  t1_lines, t1_scan    the text as one piece with the final flag, with the line
-                       path on (one launch = four kernels) and off (three)
-  t4_lines, t4_scan    four pieces of a quarter of the text each
-  t64_lines, t64_scan  64 pieces
+xmlrpc++'s encoder writes for them (--layout xmlrpc: 354,382 characters a
+chunk) or as the unbroken text a Java or Perl peer sends (--layout flat:
+349,528), built on the host slice by slice and uploaded.  One process
+alternates, round by round,
+  t1_flat, t1_lines, t1_flatonly, t1_scan
+                       the text as one piece with the final flag, on four
+                       routes: line and flat path on (one launch = five
+                       kernels), the line path alone (four; the route before
+                       the flat path existed), the flat path alone (four), and
+                       neither (three)
+  t4_*                 four pieces of a quarter of the text each
+  t64_*                64 pieces
   h1, h4, h64   lbf_sha1_update_launch alone over the decoded bytes, cut the same way
 with HIP events on the launch stream around each case's launches, after a
 warm-up, `--rounds` x `--reps` passes per figure; t - h is the decode's share,
@@ -17,8 +23,13 @@ and a case's spread is its max - min over the rounds.  After the warm-up every
 verdict must be 1, every decoded length the chunk size, and the decoded bytes
 the chunks.  Also reported: the share of each case's characters that the line
 path takes (a sample of the chains through lbf_b64_update_batch, whose context
-counts them), and what the line path's enqueue costs a call (launches of
-empty pieces, on against off, alternating).
+counts them), and what each path's enqueue costs a call (launches of
+empty pieces, route against route, alternating).
+
+  --one-shot         lbf_b64_verify_batch over 1,024 of the texts, the flat
+                     path on and off alternating: the whole host call is timed
+                     (the text's H2D included); the decode kernels' own times
+                     are read from a kernel trace, as for --general-decode
 
 Comparators from another build of the library (LBF_LIB=<its liblbfhash.so>):
   --hash-only        h1, h4, h64 alone (a library without the text entry points)
@@ -68,6 +79,61 @@ def encoder_text(chunk: np.ndarray) -> np.ndarray:
     return out
 
 
+def flat_len(size: int) -> int:
+    return 4 * ((size + 2) // 3)
+
+
+def flat_text(chunk: np.ndarray) -> np.ndarray:
+    """A Java or Perl peer's text of one chunk: RFC 4648, no separators."""
+    return np.frombuffer(base64.b64encode(chunk), dtype=np.uint8)
+
+
+def one_shot(a):
+    """lbf_b64_verify_batch on whole texts of the chosen layout, the flat path on and off in turn."""
+    import hashlib
+    n, cs = min(a.chains, 1024), a.chunk
+    dev = DeviceBuffer(n * cs)
+    dev.fill_synthetic(0x5EED)
+    H.synchronize()
+    data = dev.download(n * cs)
+    dev.free()
+    tl, text_of = (flat_len(cs), flat_text) if a.layout == "flat" else (b64_len(cs), encoder_text)
+    slot = (tl + 15) // 16 * 16
+    text = np.zeros(slot * n, dtype=np.uint8)
+    for i in range(n):
+        text[i * slot:i * slot + tl] = text_of(data[i * cs:(i + 1) * cs])
+    exp = np.frombuffer(b"".join(hashlib.sha1(data[i * cs:(i + 1) * cs]).digest() for i in range(n)), np.uint8)
+    toff = np.arange(n, dtype=np.uint64) * np.uint64(slot)
+    out = np.zeros(n * cs, dtype=np.uint8)
+    ooff = np.arange(n, dtype=np.uint64) * np.uint64(cs)
+    ms, counts, ok = {"flat_on": [], "flat_off": []}, {}, True
+    with ChunkHasher(device_mask=1) as h:
+        for on in (True, False):
+            H.set_b64_flat(on)
+            h.verify_b64(text, toff, np.full(n, tl), np.full(n, cs), exp, out, ooff)  # warm-up, scratch grown
+        for _ in range(a.rounds):
+            for name, on in (("flat_on", True), ("flat_off", False)):
+                H.set_b64_flat(on)
+                out[:] = 0
+                s0, f0 = h.b64_stats(), h.b64_flat_stats()
+                t0 = time.perf_counter()
+                for _ in range(a.reps):
+                    ver, dec = h.verify_b64(text, toff, np.full(n, tl), np.full(n, cs), exp, out, ooff)
+                ms[name].append((time.perf_counter() - t0) / a.reps * 1e3)
+                s1, f1 = h.b64_stats(), h.b64_flat_stats()
+                counts[name] = {"one_pass": (s1["one_pass"] - s0["one_pass"]) // a.reps,
+                                "general": (s1["general"] - s0["general"]) // a.reps,
+                                "flat_chunks": (f1["flat_chunks"] - f0["flat_chunks"]) // a.reps}
+                ok = ok and bool(ver.all() and (dec == cs).all() and np.array_equal(out, data))
+    want_flat = n if a.layout == "flat" else 0
+    ok = ok and counts["flat_on"]["flat_chunks"] == want_flat and counts["flat_off"]["flat_chunks"] == 0
+    res = {"mode": "one-shot", "layout": a.layout, "chunks": n, "chunk": cs, "text_chars": tl, "rounds": a.rounds,
+           "reps": a.reps, "parity": ok, "chunks_by_path": counts,
+           "host_call_ms": {k: {"median": round(statistics.median(v), 3), "min": round(min(v), 3),
+                                "max": round(max(v), 3)} for k, v in ms.items()}}
+    return res, ok
+
+
 def general_decode(a):
     """The comparator for the decode: the general kernel through the host call."""
     n, cs = min(a.chains, 1024), a.chunk
@@ -110,6 +176,8 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=120, help="seconds one case of one round may take")
     ap.add_argument("--hash-only", action="store_true")
     ap.add_argument("--general-decode", action="store_true")
+    ap.add_argument("--one-shot", action="store_true")
+    ap.add_argument("--layout", choices=("xmlrpc", "flat"), default="xmlrpc")
     ap.add_argument("--cases", default="", help="comma-separated subset of the cases (for a kernel trace of one)")
     ap.add_argument("--share-chains", type=int, default=64, help="chains of the line-share sample")
     ap.add_argument("--empty-reps", type=int, default=200, help="empty launches per round of the enqueue cost")
@@ -121,6 +189,7 @@ def main():
 
     def emit(res, ok):
         res["library"] = os.environ.get("LBF_LIB", "in-tree")
+        res.setdefault("layout", a.layout)
         line = json.dumps(res)
         print(line, flush=True)
         if a.out:
@@ -131,11 +200,13 @@ def main():
 
     if a.general_decode:
         return emit(*general_decode(a))
+    if a.one_shot:
+        return emit(*one_shot(a))
 
     sp = ctypes.c_void_p()
     check(lib.lbf_stream_create(ctypes.byref(sp)))
     stream = torch.cuda.ExternalStream(sp.value)
-    tl = b64_len(cs)
+    tl, text_of = (flat_len(cs), flat_text) if a.layout == "flat" else (b64_len(cs), encoder_text)
     slot = (tl + 15) // 16 * 16  # every text 16-byte aligned, as a receiver's frame buffer would be
     parts = (1, 4, 64)
     bufs = dict(data=DeviceBuffer(n * cs), ref=DeviceBuffer(20 * n), dig=DeviceBuffer(20 * n), sha=DeviceBuffer(96 * n),
@@ -171,7 +242,7 @@ def main():
                 host = b["data"].download(m * cs, offset=i0 * cs)
                 text = np.zeros(m * slot, dtype=np.uint8)
                 for i in range(m):
-                    text[i * slot:i * slot + tl] = encoder_text(host[i * cs:(i + 1) * cs])
+                    text[i * slot:i * slot + tl] = text_of(host[i * cs:(i + 1) * cs])
                 b["text"].upload(text, offset=i0 * slot)
             for p in parts:  # the text in p parts of (nearly) equal length
                 cut = [k * tl // p for k in range(p + 1)]
@@ -181,13 +252,23 @@ def main():
                     b["tlen", p, k].upload(np.full(n, cut[k + 1] - cut[k], dtype=np.uint32))
             b["tlen0"] = DeviceBuffer(4 * n)
             b["tlen0"].upload(np.zeros(n, dtype=np.uint32))
-        # a library from before the line path (LBF_LIB) has the general rule alone
-        routes = (("lines", True), ("scan", False)) if hasattr(lib, "lbf_set_b64_lines") else (("scan", None),)
+        # (route, line path, flat path); a library from before either path (LBF_LIB) has fewer routes
+        if hasattr(lib, "lbf_set_b64_flat"):
+            routes = (("flat", True, True), ("lines", True, False), ("flatonly", False, True), ("scan", False, False))
+        elif hasattr(lib, "lbf_set_b64_lines"):
+            routes = (("lines", True, None), ("scan", False, None))
+        else:
+            routes = (("scan", None, None),)
 
-        def text_pieces(p, lines):
+        def set_route(lines, flat):
+            if lines is not None:
+                H.set_b64_lines(lines)
+            if flat is not None:
+                H.set_b64_flat(flat)
+
+        def text_pieces(p, lines, flat):
             def run():
-                if lines is not None:
-                    H.set_b64_lines(lines)
+                set_route(lines, flat)
                 for k in range(p):
                     H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", p, k], b["tlen", p, k],
                                         b["fin1"] if k == p - 1 else b["fin0"], n, b["out"], b["ooff"], b["caps"],
@@ -203,31 +284,34 @@ def main():
                                     b["fin1"] if k == p - 1 else b["fin0"], n, b["dig"], b["ref"], b["ver"], stream=sp)
             return run
 
-        def empty_launch(lines):
+        def empty_launch(lines, flat):
             def run():
-                H.set_b64_lines(lines)
+                set_route(lines, flat)
                 H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", 1, 0], b["tlen0"], b["fin0"], n,
                                     b["out"], b["ooff"], b["caps"], b["osz"], b["dig"], b["ref"], b["ver"], b["poff"],
                                     b["psz"], stream=sp)
             return run
 
         def line_share(p):
-            """The line path's share of the characters of case t<p>: the first chains through the batch call."""
+            """The line and flat paths' shares of the characters of case t<p> with both on: the first chains
+            through the batch call."""
             m = min(a.share_chains, n)
             text = b["text"].download(m * slot)
             cut = [k * tl // p for k in range(p + 1)]
             b64s, shas = new_b64_states(m), new_states(m)
             out = np.zeros(m * cs, dtype=np.uint8)
-            H.set_b64_lines(True)
+            set_route(*routes[0][1:])
             with ChunkHasher(device_mask=1) as h:
                 for k in range(p):
                     h.update_text(b64s, shas, text, np.arange(m) * slot + cut[k], np.full(m, cut[k + 1] - cut[k]), out,
                                   np.arange(m) * cs, np.full(m, cs), final=np.full(m, k == p - 1))
                 st = h.b64_update_stats()
-            assert st["line_chars"] + st["scan_chars"] == m * tl, st
-            return round(st["line_chars"] / (m * tl), 6)
+                flat = h.b64_flat_stats()["flat_chars"] if hasattr(lib, "lbf_set_b64_flat") else 0
+            assert st["line_chars"] + st["scan_chars"] == m * tl and flat <= st["scan_chars"], (st, flat)
+            return {"line": round(st["line_chars"] / (m * tl), 6), "flat": round(flat / (m * tl), 6)}
 
-        cases = [] if a.hash_only else [(f"t{p}_{route}", text_pieces(p, on), p) for p in parts for route, on in routes]
+        cases = [] if a.hash_only else [(f"t{p}_{route}", text_pieces(p, ln, fl), p) for p in parts
+                                         for route, ln, fl in routes]
         cases += [(f"h{p}", hash_pieces(p), p) for p in parts]
         if a.cases:
             want = a.cases.split(",")  # "t4" names both of its routes, "t4_lines" one
@@ -276,22 +360,23 @@ def main():
         if not a.hash_only and not a.cases:
             res["decode_share_ms"] = {f"t{p}_{route}": round(res["cases"][f"t{p}_{route}"]["ms_per_4gib_median"] -
                                                               res["cases"][f"h{p}"]["ms_per_4gib_median"], 4)
-                                      for p in parts for route, _ in routes}
-            if len(routes) == 2:
-                res["line_share_of_chars"] = {f"t{p}": line_share(p) for p in parts}
-                us = {"lines": [], "scan": []}
-                timed(empty_launch(True), 10)
-                timed(empty_launch(False), 10)
+                                      for p in parts for route, _, _ in routes}
+            if len(routes) >= 2:
+                res["share_of_chars"] = {f"t{p}": line_share(p) for p in parts}
+                us = {route: [] for route, _, _ in routes}
+                for _, ln, fl in routes:
+                    timed(empty_launch(ln, fl), 10)
                 for _ in range(a.rounds):
-                    for route, on in routes:
-                        us[route].append(timed(empty_launch(on), a.empty_reps) * 1e3)
+                    for route, ln, fl in routes:
+                        us[route].append(timed(empty_launch(ln, fl), a.empty_reps) * 1e3)
                 med = {r: statistics.median(v) for r, v in us.items()}
-                res["empty_launch_us"] = {
-                    "pieces": n, "lines_median": round(med["lines"], 3), "scan_median": round(med["scan"], 3),
-                    "lines_min_max": [round(min(us["lines"]), 3), round(max(us["lines"]), 3)],
-                    "scan_min_max": [round(min(us["scan"]), 3), round(max(us["scan"]), 3)],
-                    "extra_enqueue_us_per_call": round(med["lines"] - med["scan"], 3)}
-                H.set_b64_lines(True)
+                res["empty_launch_us"] = {"pieces": n}
+                for r, v in us.items():
+                    res["empty_launch_us"][r] = {"median": round(med[r], 3), "min": round(min(v), 3),
+                                                 "max": round(max(v), 3)}
+                res["empty_launch_us"]["lines_enqueue_us_per_call"] = round(med["lines"] - med["scan"], 3)
+                if "flat" in med:
+                    res["empty_launch_us"]["flat_enqueue_us_per_call"] = round(med["flat"] - med["lines"], 3)
         return emit(res, all(agree.values()))
     finally:
         for buf in bufs.values():
