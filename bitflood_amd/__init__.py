@@ -11,6 +11,6 @@ See DESIGN.md for the path, the boundary and the kernels.
 from . import _capi  # noqa: F401  (imports torch first: one HIP runtime per process)
 from .hashing import (B64_STATE_DTYPE, STATE_DTYPE, ChunkHasher, DeviceBuffer, LbfError, b64_27,  # noqa: F401
                       b64_27_decode, b64_update_launch, chunk_table, new_b64_states, new_states, set_b64_flat,
-                      set_b64_lines)
+                      set_b64_fused, set_b64_lines)
 
 __version__ = "0.1.0"

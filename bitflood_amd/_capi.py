@@ -94,6 +94,7 @@ _SIGS = {
     "lbf_ctx_b64_update_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     "lbf_set_b64_flat": (_c.c_int, [_c.c_int]),
     "lbf_ctx_b64_flat_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
+    "lbf_set_b64_fused": (_c.c_int, [_c.c_int]),
     "lbf_set_kernel_variant": (_c.c_int, [_c.c_int]),
     "lbf_get_kernel_variant": (_c.c_int, []),
     "lbf_kernel_for": (_c.c_int, [_c.c_uint64]),

@@ -38,8 +38,9 @@
 //       general one.
 //
 // A translation unit of its own: the other kernels' ISA stays as recorded.
-// What it needs of kern_b64.hpp and b64_update_lines.hip (the staging, the
-// table entry, the packing) is restated here.  DESIGN.md §4.7.
+// The staging, the table entry, the packing and the piecewise stage itself
+// (flat_stage) are b64_update_stages.hpp's, which the fused kernel
+// (b64_update_fused.hip) uses too.  DESIGN.md §4.7.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdlib.h>
@@ -48,104 +49,20 @@
 #include <atomic>
 
 #include "b64_flat.hpp"
+#include "b64_update_stages.hpp"
 #include "lbf_internal.hpp"
 
 namespace lbf {
 
 namespace {
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kMaxCap = 1u << 30;        // the wire calls' bound on a chunk
-constexpr uint64_t kMaxDecoded = 1ull << 61;  // b64_update_kernel's clamp
-constexpr uint32_t kEq = 64, kSkip = 255;
-constexpr uint32_t kTileBytes = 3888, kTileGroups = kTileBytes / 3, kTileText = 4 * kTileGroups;  // 1,296 / 5,184
-constexpr uint32_t kTileBlocks = kTileBytes / 16;                                                 // 243
+using namespace b64s;
+
+// The tile of both kernels is b64_update_stages.hpp's: kTileBytes = 3888 bytes (243 blocks of 16, 1,296 groups)
+// from kTileText = 5184 characters.
+constexpr uint32_t kTileText = kFlatTileText;
+static_assert(kTileBytes == 3888 && kTileText == 5184, "the tile as stated above and in tests/wire_flat_model.py");
 constexpr uint32_t kTilesPerGroup = 4;  // the one-shot pass: consecutive tiles of a chunk per workgroup
-static_assert(kTileBytes % 48 == 0 && kTileBlocks <= kThreads, "whole groups, one 16-byte block per lane");
-// A tile's text is staged as the aligned 16-byte blocks that hold it, behind
-// kPad blocks: the first block of a piece reads its six-group window from up to
-// 20 characters in front of the piece's first group (masked, but read).
-constexpr uint32_t kPad = 2;
-constexpr uint32_t kSpan = (kTileText + 15 + 15) / 16;  // 325 blocks: a tile at any phase
-constexpr uint32_t kStage = kPad + kSpan + 2;           // and slack for the last window's 28-byte read
-constexpr uint32_t kPer = (kSpan + kThreads - 1) / kThreads;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-static_assert(sizeof(lbf_b64_state) == 16 && offsetof(lbf_b64_state, decoded) == 0 &&
-                  offsetof(lbf_b64_state, carry) == 8 && offsetof(lbf_b64_state, ncarry) == 12 &&
-                  offsetof(lbf_b64_state, ended) == 13,
-              "lbf_b64_state layout");
-
-// The decode table entry of character c: 0..63, kEq for '=', kSkip otherwise.
-__device__ __forceinline__ uint32_t value(uint32_t c) {
-  return c - 'A' < 26u ? c - 'A' : c - 'a' < 26u ? c - 'a' + 26 : c - '0' < 10u ? c - '0' + 52 :
-         c == '+' ? 62u : c == '/' ? 63u : c == '=' ? kEq : kSkip;
-}
-
-// Global bytes [src, src + len) into LDS as the aligned 16-byte blocks that
-// hold them (a block that holds one byte of the span lies in its page): LDS
-// byte 16 * kPad + (src mod 16) + k = src[k].  load() issues the loads, store()
-// waits for them, so the tile in hand decodes while the next one's text flies.
-struct Stage {
-  u32x4 v[kPer];
-  uint32_t blocks = 0;
-  __device__ __forceinline__ void load(const uint8_t* src, uint32_t len) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    const uint32_t phase = (uint32_t)(a & 15u);
-    const u32x4* g = reinterpret_cast<const u32x4*>(a - phase);
-    blocks = (phase + len + 15) / 16;  // at most kSpan
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) v[k] = __builtin_nontemporal_load(g + threadIdx.x + k * kThreads);
-  }
-  __device__ __forceinline__ void store(uint4* lds) const {
-    u32x4* l = reinterpret_cast<u32x4*>(lds) + kPad;
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) l[threadIdx.x + k * kThreads] = v[k];
-  }
-};
-
-// The lane's six groups of a tile, g0 = 16 * lane / 3 onwards, from LDS bytes
-// [c0, c0 + 24): one window of seven aligned dwords, each group cut out of it
-// with v_alignbyte.  x[j] = group j's 24 bits, joined unmasked (a flagged
-// group's bytes are never stored as data).  Table entries are 0..63, '=' 64 and
-// anything else 255, so (entry >> 6) is 0 exactly for an alphabet character:
-// two flag bits per group at 2j, for all four characters (*inner) and for the
-// first two (*head).
-__device__ __forceinline__ void six_groups(const uint8_t* sb, uint32_t c0, const uint8_t* tab, uint32_t x[6],
-                                           uint32_t* inner, uint32_t* head) {
-  const uint32_t* wb = reinterpret_cast<const uint32_t*>(sb) + (c0 >> 2);
-  const uint32_t sh = c0 & 3u;  // the same in every lane: a group is four characters
-  uint32_t win[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) win[k] = wb[k];
-  uint32_t fi = 0, fh = 0;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const uint32_t c = __builtin_amdgcn_alignbyte(win[j + 1], win[j], sh);
-    const uint32_t s0 = tab[c & 255], s1 = tab[(c >> 8) & 255], s2 = tab[(c >> 16) & 255], s3 = tab[c >> 24];
-    const uint32_t o2 = s0 | s1;
-    fi |= ((o2 | s2 | s3) >> 6) << (2 * j);
-    fh |= (o2 >> 6) << (2 * j);
-    x[j] = (((s0 << 6) | s1) << 12) | ((s2 << 6) | s3);
-  }
-  *inner = fi;
-  *head = fh;
-}
-
-// Bytes [phase, phase + 16) of the six groups' 18: group j's bytes are x[j]'s
-// bytes 2, 1, 0, one v_perm_b32 per little-endian word (selector bytes 0-3
-// pick from the second source, 4-7 from the first, 12 gives 0).
-__device__ __forceinline__ uint4 pack16(const uint32_t x[6], uint32_t phase) {
-  const uint32_t W0 = __builtin_amdgcn_perm(x[1], x[0], 0x06000102u);
-  const uint32_t W1 = __builtin_amdgcn_perm(x[2], x[1], 0x05060001u);
-  const uint32_t W2 = __builtin_amdgcn_perm(x[3], x[2], 0x04050600u);
-  const uint32_t W3 = __builtin_amdgcn_perm(x[5], x[4], 0x06000102u);
-  const uint32_t W4 = __builtin_amdgcn_perm(x[5], x[5], 0x0C0C0001u);
-  return make_uint4(__builtin_amdgcn_alignbyte(W1, W0, phase), __builtin_amdgcn_alignbyte(W2, W1, phase),
-                    __builtin_amdgcn_alignbyte(W3, W2, phase), __builtin_amdgcn_alignbyte(W4, W3, phase));
-}
 
 // The bytes of v at and past index `from` (0..16) zeroed.
 __device__ __forceinline__ uint4 zero_from(uint4 v, uint32_t from) {
@@ -154,19 +71,6 @@ __device__ __forceinline__ uint4 zero_from(uint4 v, uint32_t from) {
   for (uint32_t m = 0; m < 16; ++m)
     if (m >= from) ws[m >> 2] &= ~(255u << (8 * (m & 3)));
   return make_uint4(ws[0], ws[1], ws[2], ws[3]);
-}
-
-// Bytes [lo, hi) of the 16-byte block v to o[lo .. hi): one 16-byte store when
-// that is all of it and o is aligned, bytes otherwise.  Nothing outside is written.
-__device__ __forceinline__ void put_block(uint8_t* o, uint4 v, uint32_t lo, uint32_t hi) {
-  if (lo == 0 && hi >= 16 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-    *reinterpret_cast<uint4*>(o) = v;
-    return;
-  }
-  const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t m = 0; m < 16; ++m)
-    if (m >= lo && m < hi) o[m] = (uint8_t)(ws[m >> 2] >> (8 * (m & 3)));
 }
 
 // ---------------------------------------------------------------------------
@@ -257,149 +161,35 @@ __global__ void __launch_bounds__(kThreads) b64_update_flat_kernel(B64FlatParams
   if (si >= p.n_states) return;  // names no chain: nothing is read or written, the hand-off included
   __shared__ uint4 stage[2][kStage];
   __shared__ uint8_t tab[256];
-  __shared__ uint32_t wave_bad[2][kThreads / 64];
+  __shared__ uint32_t wave_bad[2][kWaves];
 
   uint8_t* const rec = p.b64_states + 16 * si;
-  const uint4 r = *reinterpret_cast<const uint4*>(rec);
-  uint64_t decoded = (uint64_t)r.x | ((uint64_t)r.y << 32);
-  if (decoded > kMaxDecoded) decoded = kMaxDecoded;  // b64_update_kernel's clamps, all three
-  const uint32_t nc = r.w & 3u;
-  const uint32_t carry = r.z & ((1u << (6u * nc)) - 1u);
-  const bool ended = ((r.w >> 8) & 0xFFu) != 0;
+  Rec r = read_rec(rec);
+  const uint64_t decoded = r.decoded;
   const uint32_t cap = p.cap[i], piece_len = p.text_len[i];
   uint32_t skip = 0;  // the characters the line kernel took
   if (p.after_lines) {
     skip = p.taken[i];
     if (skip > piece_len) skip = piece_len;  // never: the line path takes a prefix
   }
-  const uint32_t len = piece_len - skip;
-  // a record the batch call would refuse, or nothing to take: the rest is b64_update_kernel's whole
-  if (cap > kMaxCap || ended || decoded % 3 != 0 || len == 0) {
-    if (threadIdx.x == 0) {
-      if (!p.after_lines) {
-        p.before[i] = decoded;
-        p.taken[i] = 0;
-      }
-      if (p.flat_chars) p.flat_chars[i] = 0;
-    }
-    return;  // the whole workgroup: every value above is the same in every lane
+  uint32_t took = 0;
+  // a chunk or a record the batch call would refuse, or no text left: the rest is b64_update_kernel's whole (the
+  // whole workgroup: every value is the same in every lane)
+  if (cap <= kMaxCap && !nothing_to_take(r, piece_len - skip)) {
+    tab[threadIdx.x] = (uint8_t)value(threadIdx.x);
+    const Piece pc{p.text + p.text_off[i] + skip, piece_len - skip, p.out, p.out_off[i], cap};
+    took = flat_stage(r, pc, stage, tab, wave_bad);
   }
-  const uint8_t* const t = p.text + p.text_off[i] + skip;
-  const uint64_t slot = p.out_off[i];  // positions are sums of 64-bit numbers, taken mod 2^64
-  tab[threadIdx.x] = (uint8_t)value(threadIdx.x);
-
-  // ---- the head: the carried group.  Every lane works it out; lane 0 writes.
-  uint64_t D = decoded;  // bytes of the chain decoded so far; a multiple of 3 from here on
-  uint32_t pos = 0;      // characters of the remainder taken so far
-  bool go = true;
-  if (nc != 0) {
-    const uint32_t need = 4 - nc;
-    uint32_t x = 0, junk = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 3; ++k)
-      if (k < nc) x |= ((carry >> (6u * k)) & 63u) << (18u - 6u * k);
-    if (len < need) {
-      go = false;
-    } else {
-#pragma unroll
-      for (uint32_t k = 1; k < 4; ++k) {
-        if (k < nc) continue;
-        const uint32_t v = value(t[k - nc]);
-        junk |= v >> 6;
-        x |= (v & 63u) << (18u - 6u * k);
-      }
-      go = junk == 0;
+  if (threadIdx.x == 0) {
+    if (r.decoded != decoded) *reinterpret_cast<uint4*>(rec) = rec_words(r);  // behind a group: nothing is carried
+    if (!p.after_lines) {
+      p.before[i] = decoded;
+      p.taken[i] = took;
+    } else if (took) {  // behind the line kernel both entries are written already
+      p.taken[i] = skip + took;
     }
-    if (go) {
-      if (threadIdx.x == 0) {
-        uint8_t* const o = p.out + (slot + D);
-        if (D < cap) o[0] = (uint8_t)(x >> 16);
-        if (D + 1 < cap) o[1] = (uint8_t)(x >> 8);
-        if (D + 2 < cap) o[2] = (uint8_t)x;
-      }
-      D += 3;  // at most 2^61 + 1: no wrap
-      pos = need;
-    }
+    if (p.flat_chars) p.flat_chars[i] = took;
   }
-  uint32_t groups = 0;  // whole groups that follow, by the remainder's length
-  if (go) {
-    groups = (len - pos) / 4;
-    if (groups) {  // '=' stops the prefix: only the last group of a text holds it
-      const uint8_t* const g = t + pos + 4 * (groups - 1);
-      if (g[0] == '=' || g[1] == '=' || g[2] == '=' || g[3] == '=') --groups;
-    }
-  }
-
-  // ---- the tiles of the chunk that hold groups [D / 3, D / 3 + groups)
-  uint32_t done = 0;  // groups of validated tiles
-  if (groups) {
-    const uint64_t tile0 = D / kTileBytes;
-    const uint32_t g_first = (uint32_t)(D - tile0 * kTileBytes) / 3;  // the first group's index in its tile
-    const uint32_t g_end = g_first + groups;                          // < 2^30 + 1,296
-    const uint32_t ntiles = (g_end + kTileGroups - 1) / kTileGroups;
-    Stage st;
-    uint32_t delta_next = 0;
-    // tile j's groups [gl, gh) of the tile; character c of the tile is character pos + (5184 j + c) - 4 g_first
-    // of the remainder
-    auto load = [&](uint32_t j) {
-      const uint32_t gl = j == 0 ? g_first : 0u;
-      const uint32_t gh = g_end - j * kTileGroups < kTileGroups ? g_end - j * kTileGroups : kTileGroups;
-      const uint8_t* const src = t + pos + ((uint64_t)j * kTileText + 4 * gl - 4 * g_first);
-      st.load(src, 4 * (gh - gl));
-      delta_next = 16 * kPad + (uint32_t)(reinterpret_cast<uintptr_t>(src) & 15u) - 4 * gl;  // mod 2^32
-    };
-    load(0);
-    st.store(stage[0]);
-    uint32_t delta = delta_next;
-    __syncthreads();  // the table and tile 0's text
-    for (uint32_t j = 0; j < ntiles; ++j) {
-      const uint32_t buf = j & 1u;
-      const bool next = j + 1 < ntiles;
-      if (next) load(j + 1);  // in flight while this tile decodes
-      const uint32_t gl = j == 0 ? g_first : 0u;
-      const uint32_t gh = g_end - j * kTileGroups < kTileGroups ? g_end - j * kTileGroups : kTileGroups;
-      const uint32_t b0 = 16 * threadIdx.x;
-      // the lanes whose block holds a byte of groups [gl, gh)
-      const bool mine = threadIdx.x < kTileBlocks && b0 + 16 > 3 * gl && b0 < 3 * gh;
-      bool bad = false;
-      uint4 v = make_uint4(0u, 0u, 0u, 0u);
-      if (mine) {
-        // g0 >= gl - 5 and g0 < gh: the window starts at most 20 characters in front of the staged text (the pad)
-        const uint32_t g0 = b0 / 3, phase = b0 - 3 * g0;
-        uint32_t x[6], inner, head;
-        six_groups(reinterpret_cast<const uint8_t*>(stage[buf]), delta + 4 * g0, tab, x, &inner, &head);
-        const uint32_t jl = gl > g0 ? gl - g0 : 0u, jh = gh - g0 < 6u ? gh - g0 : 6u;
-        bad = (inner & ((1u << (2 * jh)) - 1u) & ~((1u << (2 * jl)) - 1u)) != 0;  // the piece's groups only
-        v = pack16(x, phase);
-      }
-      const bool wave_has = __ballot(bad) != 0;
-      if ((threadIdx.x & 63u) == 0) wave_bad[buf][threadIdx.x >> 6] = wave_has ? 1u : 0u;
-      if (next) {
-        st.store(stage[buf ^ 1u]);  // that buffer's last readers were the previous tile's lanes, before its barrier
-        delta = delta_next;
-      }
-      __syncthreads();  // the flags of this tile, the text of the next
-      // (wave_bad[buf] is written again two tiles on, behind the next tile's barrier)
-      if (wave_bad[buf][0] | wave_bad[buf][1] | wave_bad[buf][2] | wave_bad[buf][3]) break;  // the whole workgroup
-      done += gh - gl;
-      if (!mine) continue;
-      // the tile is good: the block's bytes that are the piece's and lie below cap
-      const uint64_t tb = (tile0 + j) * kTileBytes;  // at most 2^61 + 3,888
-      const uint32_t in_cap = cap > tb ? (cap - tb < kTileBytes ? (uint32_t)(cap - tb) : kTileBytes) : 0u;
-      const uint32_t wlo = 3 * gl, whi = 3 * gh < in_cap ? 3 * gh : in_cap;
-      if (whi > b0)
-        put_block(p.out + (slot + tb + b0), v, wlo > b0 ? wlo - b0 : 0u, whi - b0);
-    }
-  }
-  if (threadIdx.x != 0) return;
-  const uint32_t took = go ? pos + 4 * done : 0u;
-  const uint64_t now = D + 3ull * done;
-  if (go && now != decoded)  // the prefix ends behind a group: nothing is carried
-    *reinterpret_cast<uint4*>(rec) = make_uint4((uint32_t)(now < kMaxDecoded ? now : kMaxDecoded),
-                                                (uint32_t)((now < kMaxDecoded ? now : kMaxDecoded) >> 32), 0u, 0u);
-  if (!p.after_lines) p.before[i] = decoded;
-  p.taken[i] = skip + took;
-  if (p.flat_chars) p.flat_chars[i] = took;
 }
 
 }  // namespace

@@ -18,7 +18,10 @@
 // and hands over, through the piece table's two arrays, where the chain stood
 // and how many characters it took; unbroken text in what that left is taken
 // next by b64_flat.hip's kernel (lbf_set_b64_flat), which hands over the same
-// two numbers; this kernel decodes what is left.
+// two numbers; this kernel decodes what is left.  With lbf_set_b64_fused on,
+// one kernel (b64_update_fused.hip) runs the three stages of a piece in one
+// launch instead, and the two switches are its stage mask.  All four kernels
+// are built from the stage functions of b64_update_stages.hpp.
 //
 // A translation unit of its own, like sha1_update.hip: the shipped kernels'
 // ISA stays as recorded (tests/test_isa.py).  DESIGN.md §4.7.
@@ -29,7 +32,9 @@
 #include <atomic>
 
 #include "b64_flat.hpp"
+#include "b64_update_fused.hpp"
 #include "b64_update_lines.hpp"
+#include "b64_update_stages.hpp"
 #include "lbf_internal.hpp"
 
 namespace lbf {
@@ -56,67 +61,10 @@ struct B64UpdateParams {
   uint32_t lines;
 };
 
-constexpr uint32_t kThreads = 256;
-constexpr uint32_t kTrip = kThreads * 16;  // characters per trip, as the general decode (kern_b64.hpp)
-constexpr uint32_t kMaxCap = 1u << 30;     // the wire calls' bound on a chunk
-constexpr uint8_t kEq = 64, kSkip = 255;
-// A chain's byte count stays at or below this (the host call refuses a record at
-// or past it).  The kernel clamps what it loads to it and a piece adds less than
-// 2^32, so no position below ever wraps, whatever a forged record claims.
-constexpr uint64_t kMaxDecoded = 1ull << 61;
+using namespace b64s;
 
-static_assert(sizeof(lbf_b64_state) == 16 && offsetof(lbf_b64_state, decoded) == 0 &&
-                  offsetof(lbf_b64_state, carry) == 8 && offsetof(lbf_b64_state, ncarry) == 12 &&
-                  offsetof(lbf_b64_state, ended) == 13 && offsetof(lbf_b64_state, zero) == 14,
-              "lbf_b64_state layout");
-
-// The decode table of kern_b64.hpp, restated: that header belongs to
-// sha1_kernels.hip's translation unit.
-struct Table {
-  uint8_t v[256];
-};
-
-constexpr Table make_table() {
-  Table t{};
-  for (int c = 0; c < 256; ++c) t.v[c] = kSkip;
-  for (int c = 'A'; c <= 'Z'; ++c) t.v[c] = (uint8_t)(c - 'A');
-  for (int c = 'a'; c <= 'z'; ++c) t.v[c] = (uint8_t)(26 + c - 'a');
-  for (int c = '0'; c <= '9'; ++c) t.v[c] = (uint8_t)(52 + c - '0');
-  t.v['+'] = 62;
-  t.v['/'] = 63;
-  t.v['='] = kEq;
-  return t;
-}
-
-__constant__ Table g_update_table = make_table();
-
-// Exclusive scan of one value per lane over the workgroup (wg_exclusive_scan's
-// shape, kern_b64.hpp); `sums` is 4 words of LDS.
-__device__ __forceinline__ uint32_t scan256(uint32_t v, uint32_t* sums, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) sums[wave] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < (int)kThreads / 64; ++w) {
-    const uint32_t s = sums[w];
-    before += w < wave ? s : 0u;
-    all += s;
-  }
-  __syncthreads();  // sums is reused by the next trip
-  *total = all;
-  return before + x - v;
-}
-
-// blockIdx.x = piece.  The sextets of a trip go through LDS: sx[0, nc) holds
-// the carried sextets, the trip's own follow, so group g of the trip is sx[4g,
-// 4g + 4) and a lane's four groups are one aligned 16-byte LDS read.
+// blockIdx.x = piece.  The trips are scan_stage's (b64_update_stages.hpp), which
+// the fused kernel (b64_update_fused.hip) runs too.
 __global__ void __launch_bounds__(kThreads) b64_update_kernel(B64UpdateParams p) {
   const uint32_t i = blockIdx.x;
   const uint64_t si = p.state_of ? (uint64_t)p.state_of[i] : (uint64_t)i;
@@ -135,156 +83,27 @@ __global__ void __launch_bounds__(kThreads) b64_update_kernel(B64UpdateParams p)
     }
     return;
   }
-  __shared__ __attribute__((aligned(16))) uint8_t sx[kTrip + 16];  // 4,096 + 3 sextets, whole 16-byte blocks
+  __shared__ __attribute__((aligned(16))) uint8_t sx[kSx];
   __shared__ uint8_t tab[256];
-  __shared__ uint32_t sums[kThreads / 64];
+  __shared__ uint32_t sums[kWaves];
   __shared__ uint32_t first_eq;
 
   uint8_t* const rec = p.b64_states + 16 * si;
-  const uint4 r = *reinterpret_cast<const uint4*>(rec);
-  uint64_t decoded = (uint64_t)r.x | ((uint64_t)r.y << 32);
-  if (decoded > kMaxDecoded) decoded = kMaxDecoded;  // forged: far past any slot, and it stays there
-  // & 3 and the mask: whatever a forged record says, the carry is at most three sextets
-  uint32_t nc = r.w & 3u;
-  const uint32_t carry = r.z & ((1u << (6u * nc)) - 1u);
-  bool ended = ((r.w >> 8) & 0xFFu) != 0;
-  uint64_t before = decoded < cap ? decoded : (uint64_t)cap;
+  Rec r = read_rec(rec);
+  uint64_t start = r.decoded;
   uint32_t taken = 0;
   if (p.lines) {  // the record has moved on by what the line path took: the piece's share starts where it started
-    const uint64_t b = p.piece_off[i];
-    before = b < cap ? b : (uint64_t)cap;
+    start = p.piece_off[i];
     taken = p.piece_size[i];
   }
-
-  tab[threadIdx.x] = g_update_table.v[threadIdx.x];
-  if (threadIdx.x < 3) sx[threadIdx.x] = (uint8_t)((carry >> (6u * threadIdx.x)) & 63u);
-  if (threadIdx.x == 0) first_eq = 0xFFFFFFFFu;
-  __syncthreads();
-
+  tab[threadIdx.x] = (uint8_t)value(threadIdx.x);
   const uint32_t piece_len = p.text_len[i];
   if (taken > piece_len) taken = piece_len;  // never: the line path takes a prefix
-  const uint8_t* const t = p.text + p.text_off[i] + taken;
-  const uint64_t len = ended ? 0 : piece_len - taken;
-  const uint64_t slot = p.out_off[i];  // positions are sums of 64-bit numbers, taken mod 2^64
-  for (uint64_t t0 = 0; t0 < len; t0 += kTrip) {
-    // 1. sixteen characters per lane; the ragged end reads as junk
-    const uint64_t at = t0 + threadIdx.x * 16u;
-    uint8_t c[16];
-    if (at + 16 <= len) {
-      const uintptr_t a = reinterpret_cast<uintptr_t>(t + at);
-      if ((a & 3u) == 0) {
-        uint32_t w[4];
-        if ((a & 15u) == 0) {
-          const uint4 q = *reinterpret_cast<const uint4*>(t + at);
-          w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        } else {
-          const uint32_t* q = reinterpret_cast<const uint32_t*>(t + at);
-#pragma unroll
-          for (int k = 0; k < 4; ++k) w[k] = q[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 16; ++k) c[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
-      } else {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) c[k] = t[at + k];
-      }
-    } else {
-#pragma unroll
-      for (int k = 0; k < 16; ++k) c[k] = at + k < len ? t[at + k] : (uint8_t)' ';
-    }
-    // 2. look up, count; 3. the lane's place among the trip's sextets
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      c[k] = tab[c[k]];
-      cnt += c[k] != kSkip;
-    }
-    uint32_t total;
-    uint32_t pos = nc + scan256(cnt, sums, &total);
-    // 4. sextets behind the carry; 5. the first '='.  pos < nc + 4,096 <= 4,099
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      if (c[k] == kSkip) continue;
-      if (c[k] == kEq) atomicMin(&first_eq, pos);
-      sx[pos++] = c[k];
-    }
-    __syncthreads();
-    // 6. complete groups before any '='
-    const uint32_t m = nc + total, feq = first_eq;
-    const uint32_t q = feq < m ? feq : m;
-    const uint32_t groups = q >> 2, rest = q & 3u;
-    // 7. four groups (16 sextets) -> 12 bytes per lane, never at or past cap
-    const uint32_t g4 = threadIdx.x * 4u;
-    if (g4 < groups) {
-      const uint4 v4 = *reinterpret_cast<const uint4*>(sx + 4u * g4);
-      const uint32_t vs[4] = {v4.x, v4.y, v4.z, v4.w};
-      uint32_t x[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t s = vs[k];  // sextets past the complete groups are stale, and their bytes are not written
-        x[k] = ((s & 63u) << 18) | (((s >> 8) & 63u) << 12) | (((s >> 16) & 63u) << 6) | ((s >> 24) & 63u);
-      }
-      uint8_t b[12];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        b[3 * k] = (uint8_t)(x[k] >> 16);
-        b[3 * k + 1] = (uint8_t)(x[k] >> 8);
-        b[3 * k + 2] = (uint8_t)x[k];
-      }
-      const uint64_t at_out = decoded + 3ull * g4;  // position in the chunk: at most 2^61 + 3,060, no wrap
-      const uint32_t left = groups - g4;
-      const uint32_t nb = left >= 4 ? 12u : 3u * left;
-      uint8_t* const o = p.out + (slot + at_out);
-      if (nb == 12 && cap >= 12u && at_out <= cap - 12u && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
-        uint32_t* d = reinterpret_cast<uint32_t*>(o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-          d[k] = (uint32_t)b[4 * k] | ((uint32_t)b[4 * k + 1] << 8) | ((uint32_t)b[4 * k + 2] << 16) |
-                 ((uint32_t)b[4 * k + 3] << 24);
-      } else {
-        for (uint32_t k = 0; k < nb && at_out + k < cap; ++k) o[k] = b[k];
-      }
-    }
-    const uint64_t at_end = decoded + 3ull * groups;
-    if (feq < m) {
-      // 8. '=' ends the data: "xx=" gives one more byte, "xxx=" two
-      const uint32_t extra = rest == 2 ? 1u : rest == 3 ? 2u : 0u;
-      if (threadIdx.x == 0 && extra) {
-        const uint32_t a = 4u * groups;
-        const uint32_t x = ((uint32_t)sx[a] << 18) | ((uint32_t)sx[a + 1] << 12) |
-                           ((uint32_t)(extra == 2 ? sx[a + 2] : 0) << 6);
-        uint8_t* const o = p.out + (slot + at_end);
-        if (at_end < cap) o[0] = (uint8_t)(x >> 16);
-        if (extra == 2 && at_end + 1 < cap) o[1] = (uint8_t)(x >> 8);
-      }
-      decoded = at_end + extra < kMaxDecoded ? at_end + extra : kMaxDecoded;
-      ended = true;
-      nc = 0;
-      break;  // uniform: feq and m are the same in every lane
-    }
-    // 9. the unfinished group moves to the front for the next trip
-    decoded = at_end < kMaxDecoded ? at_end : kMaxDecoded;
-    uint8_t keep = 0;
-    if (threadIdx.x < rest) keep = sx[4u * groups + threadIdx.x];
-    __syncthreads();  // every read of this trip's sextets is done
-    if (threadIdx.x < rest) sx[threadIdx.x] = keep;
-    nc = rest;
-    // the next trip's barriers (in its scan) come before any lane reads sx again
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const uint64_t after = decoded < cap ? decoded : (uint64_t)cap;
-  p.piece_off[i] = slot + before;
-  p.piece_size[i] = after > before ? (uint32_t)(after - before) : 0u;  // decoded never falls; checked all the same
-  uint4 w = make_uint4(0u, 0u, 0u, 0u);  // as lbf_b64_state_init leaves it: Final() restarts the chain
-  if (fin) {
-    p.out_sizes[i] = decoded <= cap ? (uint32_t)decoded : cap + 1u;  // an unfinished group is dropped
-  } else {
-    uint32_t cw = 0;
-    for (uint32_t k = 0; k < nc; ++k) cw |= (uint32_t)(sx[k] & 63u) << (6u * k);
-    w = make_uint4((uint32_t)decoded, (uint32_t)(decoded >> 32), cw, nc | (ended ? 0x100u : 0u));
-  }
-  *reinterpret_cast<uint4*>(rec) = w;
+  const uint64_t slot = p.out_off[i];
+  const Piece pc{p.text + p.text_off[i] + taken, piece_len - taken, p.out, slot, cap};
+  scan_stage(r, pc, sx, tab, sums, &first_eq);
+  if (threadIdx.x == 0)
+    finish_piece(r, start, slot, cap, fin, rec, p.piece_off + i, p.piece_size + i, p.out_sizes + i);
 }
 
 // A final piece's verdict holds only when its text decoded to the chunk's size
@@ -408,43 +227,65 @@ int lbf::b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* 
   p.piece_size = d_piece_sizes;
   p.verdicts = d_verdicts;
   hipStream_t st = (hipStream_t)stream;
-  if (lbf::b64_lines_enabled()) {  // the text that continues the encoder's layout, in front of the general rule
-    lbf::B64LinesParams lp{};
-    lp.b64_states = p.b64_states;
-    lp.n_states = n_states;
-    lp.state_of = d_state_of;
-    lp.text = p.text;
-    lp.text_off = d_text_offsets;
-    lp.text_len = d_text_lens;
-    lp.out = d_out;
-    lp.out_off = d_out_offsets;
-    lp.cap = d_caps;
-    lp.before = d_piece_offsets;
-    lp.taken = d_piece_sizes;
-    lp.line_chars = d_line_chars;
-    if (int rc = lbf::launch_b64_update_lines(lp, (uint32_t)n, st)) return rc;
-    p.lines = 1;
+  if (lbf::b64_fused_enabled()) {  // the three decode kernels in one launch; the two switches are its stage mask
+    lbf::B64FusedParams f{};
+    f.b64_states = p.b64_states;
+    f.n_states = n_states;
+    f.state_of = d_state_of;
+    f.text = p.text;
+    f.text_off = d_text_offsets;
+    f.text_len = d_text_lens;
+    f.final_flags = d_final;
+    f.out = d_out;
+    f.out_off = d_out_offsets;
+    f.cap = d_caps;
+    f.out_sizes = d_out_sizes;
+    f.piece_off = d_piece_offsets;
+    f.piece_size = d_piece_sizes;
+    f.line_chars = d_line_chars;
+    f.flat_chars = d_flat_chars;
+    f.stages = (lbf::b64_lines_enabled() ? lbf::kB64StageLines : 0u) |
+               (lbf::b64_flat_enabled() ? lbf::kB64StageFlat : 0u);
+    if (int rc = lbf::launch_b64_update_fused(f, (uint32_t)n, st)) return rc;
+  } else {
+    if (lbf::b64_lines_enabled()) {  // the text that continues the encoder's layout, in front of the general rule
+      lbf::B64LinesParams lp{};
+      lp.b64_states = p.b64_states;
+      lp.n_states = n_states;
+      lp.state_of = d_state_of;
+      lp.text = p.text;
+      lp.text_off = d_text_offsets;
+      lp.text_len = d_text_lens;
+      lp.out = d_out;
+      lp.out_off = d_out_offsets;
+      lp.cap = d_caps;
+      lp.before = d_piece_offsets;
+      lp.taken = d_piece_sizes;
+      lp.line_chars = d_line_chars;
+      if (int rc = lbf::launch_b64_update_lines(lp, (uint32_t)n, st)) return rc;
+      p.lines = 1;
+    }
+    if (lbf::b64_flat_enabled()) {  // unbroken text in what is left: the same hand-over
+      lbf::B64FlatParams fp{};
+      fp.b64_states = p.b64_states;
+      fp.n_states = n_states;
+      fp.state_of = d_state_of;
+      fp.text = p.text;
+      fp.text_off = d_text_offsets;
+      fp.text_len = d_text_lens;
+      fp.out = d_out;
+      fp.out_off = d_out_offsets;
+      fp.cap = d_caps;
+      fp.before = d_piece_offsets;
+      fp.taken = d_piece_sizes;
+      fp.flat_chars = d_flat_chars;
+      fp.after_lines = p.lines;
+      if (int rc = lbf::launch_b64_update_flat(fp, (uint32_t)n, st)) return rc;
+      p.lines = 1;
+    }
+    hipLaunchKernelGGL(lbf::b64_update_kernel, dim3((uint32_t)n), dim3(lbf::kThreads), 0, st, p);
+    LBF_HIP_TRY(hipGetLastError());
   }
-  if (lbf::b64_flat_enabled()) {  // unbroken text in what is left: the same hand-over, from or behind the line path's
-    lbf::B64FlatParams fp{};
-    fp.b64_states = p.b64_states;
-    fp.n_states = n_states;
-    fp.state_of = d_state_of;
-    fp.text = p.text;
-    fp.text_off = d_text_offsets;
-    fp.text_len = d_text_lens;
-    fp.out = d_out;
-    fp.out_off = d_out_offsets;
-    fp.cap = d_caps;
-    fp.before = d_piece_offsets;
-    fp.taken = d_piece_sizes;
-    fp.flat_chars = d_flat_chars;
-    fp.after_lines = p.lines;
-    if (int rc = lbf::launch_b64_update_flat(fp, (uint32_t)n, st)) return rc;
-    p.lines = 1;
-  }
-  hipLaunchKernelGGL(lbf::b64_update_kernel, dim3((uint32_t)n), dim3(lbf::kThreads), 0, st, p);
-  LBF_HIP_TRY(hipGetLastError());
   if (int rc = lbf_sha1_update_launch(d_sha_states, n_states, d_state_of, d_out, d_piece_offsets, d_piece_sizes,
                                       d_final, n, d_digests, d_expected, d_verdicts, st))
     return rc;

@@ -549,6 +549,14 @@ def set_b64_flat(on) -> bool:
     return bool(load().lbf_set_b64_flat(1 if on else 0))
 
 
+def set_b64_fused(on) -> bool:
+    """lbf_set_b64_fused: the fused route of update_text / b64_update_launch (the
+    line, flat and scan stages of a piece in one kernel launch, set_b64_lines
+    and set_b64_flat as its stage mask) on or off, process-wide; returns the
+    previous setting."""
+    return bool(load().lbf_set_b64_fused(1 if on else 0))
+
+
 def synchronize():
     check(load().lbf_device_synchronize())
 
@@ -559,5 +567,5 @@ def set_kernel_variant(v: int):
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
-           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "set_b64_flat", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

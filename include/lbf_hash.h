@@ -328,7 +328,9 @@ void lbf_b64_state_init(lbf_b64_state* states, uint64_t n);
 
 /* Device-resident and asynchronous on `stream`: four enqueues (three with the
  * line path off, lbf_set_b64_lines) and one more with the flat path on
- * (lbf_set_b64_flat), no host round trip, no device allocation.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
+ * (lbf_set_b64_flat) -- or three in all on the fused route (lbf_set_b64_fused,
+ * below: one decode kernel in place of up to three) -- no host round trip, no
+ * device allocation.  Piece i = the text d_text[d_text_offsets[i], + d_text_lens[i])
  * continues chain d_state_of[i] (chain i when d_state_of is NULL): the pair
  * d_b64_states[s], d_sha_states[s] of n_states pairs (both arrays 16-byte
  * aligned).  Its chunk's slot is d_out[d_out_offsets[i], + d_caps[i]) -- the
@@ -401,6 +403,23 @@ int lbf_set_b64_flat(int on);
  * took -- a sub-count of lbf_ctx_b64_update_stats' scan_chars, which keeps
  * counting every character the line path did not take. */
 int lbf_ctx_b64_flat_stats(lbf_ctx* ctx, uint64_t* flat_chunks, uint64_t* flat_chars);
+/* The fused route of lbf_b64_update_launch / lbf_b64_update_batch,
+ * process-wide: anything but 0 switches it on, 0 off (the enqueues are exactly
+ * those described above).  Returns the previous value.  Until the first launch
+ * or call of this function the value is LBF_B64_FUSED's (default off; "1" =
+ * on).  On, a launch is three enqueues whatever the other two switches say:
+ * one decode kernel (one workgroup per piece) that reads the chain's record
+ * once, runs the line path's, the flat path's and the general rule's stages on
+ * the piece one after the other with the record in registers, and writes the
+ * record and the work arrays once; then lbf_sha1_update_launch and the length
+ * check as above.  lbf_set_b64_lines and lbf_set_b64_flat then say which
+ * stages run in front of the general rule; which stage takes which characters
+ * of a piece is decided on the device from the text, piece by piece, so text
+ * in the encoder's layout and unbroken text may share a launch with both on.
+ * Bytes, records, lengths, verdicts, the work arrays and the per-path counters
+ * (lbf_ctx_b64_update_stats, lbf_ctx_b64_flat_stats) are the same on both
+ * routes, to the character. */
+int lbf_set_b64_fused(int on);
 /* The same over host memory, synchronous on the context's first device.  Piece
  * i = text[text_offsets[i], + text_lens[i]) of chain state_of[i], whose chunk
  * is expected_sizes[i] bytes and lives at out[out_offsets[i], +

@@ -11,9 +11,12 @@ alternates, round by round,
   t1_flat, t1_lines, t1_flatonly, t1_scan
                        the text as one piece with the final flag, on four
                        routes: line and flat path on (one launch = five
-                       kernels), the line path alone (four; the route before
-                       the flat path existed), the flat path alone (four), and
-                       neither (three)
+                       kernels), the line path alone (four; the default route),
+                       the flat path alone (four), and neither (three)
+  t1_fused, t1_fusedlines
+                       the same on the fused route (lbf_set_b64_fused: three
+                       kernels whatever the stage mask): line and flat stage on,
+                       and the line stage alone
   t4_*                 four pieces of a quarter of the text each
   t64_*                64 pieces
   h1, h4, h64   lbf_sha1_update_launch alone over the decoded bytes, cut the same way
@@ -252,23 +255,30 @@ def main():
                     b["tlen", p, k].upload(np.full(n, cut[k + 1] - cut[k], dtype=np.uint32))
             b["tlen0"] = DeviceBuffer(4 * n)
             b["tlen0"].upload(np.zeros(n, dtype=np.uint32))
-        # (route, line path, flat path); a library from before either path (LBF_LIB) has fewer routes
+        # (route, line path, flat path, fused route); a library from before a path or the fused route (LBF_LIB) has
+        # fewer routes
         if hasattr(lib, "lbf_set_b64_flat"):
-            routes = (("flat", True, True), ("lines", True, False), ("flatonly", False, True), ("scan", False, False))
+            off = False if hasattr(lib, "lbf_set_b64_fused") else None
+            routes = (("flat", True, True, off), ("lines", True, False, off), ("flatonly", False, True, off),
+                      ("scan", False, False, off))
+            if off is not None:
+                routes += (("fused", True, True, True), ("fusedlines", True, False, True))
         elif hasattr(lib, "lbf_set_b64_lines"):
-            routes = (("lines", True, None), ("scan", False, None))
+            routes = (("lines", True, None, None), ("scan", False, None, None))
         else:
-            routes = (("scan", None, None),)
+            routes = (("scan", None, None, None),)
 
-        def set_route(lines, flat):
+        def set_route(lines, flat, fused):
             if lines is not None:
                 H.set_b64_lines(lines)
             if flat is not None:
                 H.set_b64_flat(flat)
+            if fused is not None:
+                H.set_b64_fused(fused)
 
-        def text_pieces(p, lines, flat):
+        def text_pieces(p, *route):
             def run():
-                set_route(lines, flat)
+                set_route(*route)
                 for k in range(p):
                     H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", p, k], b["tlen", p, k],
                                         b["fin1"] if k == p - 1 else b["fin0"], n, b["out"], b["ooff"], b["caps"],
@@ -284,23 +294,23 @@ def main():
                                     b["fin1"] if k == p - 1 else b["fin0"], n, b["dig"], b["ref"], b["ver"], stream=sp)
             return run
 
-        def empty_launch(lines, flat):
+        def empty_launch(*route):
             def run():
-                set_route(lines, flat)
+                set_route(*route)
                 H.b64_update_launch(b["b64"], b["sha"], n, None, b["text"], b["toff", 1, 0], b["tlen0"], b["fin0"], n,
                                     b["out"], b["ooff"], b["caps"], b["osz"], b["dig"], b["ref"], b["ver"], b["poff"],
                                     b["psz"], stream=sp)
             return run
 
-        def line_share(p):
-            """The line and flat paths' shares of the characters of case t<p> with both on: the first chains
+        def line_share(p, route):
+            """The line and flat paths' shares of the characters of case t<p> on `route`: the first chains
             through the batch call."""
             m = min(a.share_chains, n)
             text = b["text"].download(m * slot)
             cut = [k * tl // p for k in range(p + 1)]
             b64s, shas = new_b64_states(m), new_states(m)
             out = np.zeros(m * cs, dtype=np.uint8)
-            set_route(*routes[0][1:])
+            set_route(*route)
             with ChunkHasher(device_mask=1) as h:
                 for k in range(p):
                     h.update_text(b64s, shas, text, np.arange(m) * slot + cut[k], np.full(m, cut[k + 1] - cut[k]), out,
@@ -310,8 +320,8 @@ def main():
             assert st["line_chars"] + st["scan_chars"] == m * tl and flat <= st["scan_chars"], (st, flat)
             return {"line": round(st["line_chars"] / (m * tl), 6), "flat": round(flat / (m * tl), 6)}
 
-        cases = [] if a.hash_only else [(f"t{p}_{route}", text_pieces(p, ln, fl), p) for p in parts
-                                         for route, ln, fl in routes]
+        cases = [] if a.hash_only else [(f"t{p}_{route}", text_pieces(p, *how), p) for p in parts
+                                         for route, *how in routes]
         cases += [(f"h{p}", hash_pieces(p), p) for p in parts]
         if a.cases:
             want = a.cases.split(",")  # "t4" names both of its routes, "t4_lines" one
@@ -360,15 +370,17 @@ def main():
         if not a.hash_only and not a.cases:
             res["decode_share_ms"] = {f"t{p}_{route}": round(res["cases"][f"t{p}_{route}"]["ms_per_4gib_median"] -
                                                               res["cases"][f"h{p}"]["ms_per_4gib_median"], 4)
-                                      for p in parts for route, _, _ in routes}
+                                      for p in parts for route, *_ in routes}
             if len(routes) >= 2:
-                res["share_of_chars"] = {f"t{p}": line_share(p) for p in parts}
-                us = {route: [] for route, _, _ in routes}
-                for _, ln, fl in routes:
-                    timed(empty_launch(ln, fl), 10)
+                res["share_of_chars"] = {f"t{p}": line_share(p, routes[0][1:]) for p in parts}
+                if len(routes) > 4:  # the same characters by the same paths on the fused route
+                    res["share_of_chars_fused"] = {f"t{p}": line_share(p, routes[4][1:]) for p in parts}
+                us = {route: [] for route, *_ in routes}
+                for _, *how in routes:
+                    timed(empty_launch(*how), 10)
                 for _ in range(a.rounds):
-                    for route, ln, fl in routes:
-                        us[route].append(timed(empty_launch(ln, fl), a.empty_reps) * 1e3)
+                    for route, *how in routes:
+                        us[route].append(timed(empty_launch(*how), a.empty_reps) * 1e3)
                 med = {r: statistics.median(v) for r, v in us.items()}
                 res["empty_launch_us"] = {"pieces": n}
                 for r, v in us.items():
@@ -377,6 +389,9 @@ def main():
                 res["empty_launch_us"]["lines_enqueue_us_per_call"] = round(med["lines"] - med["scan"], 3)
                 if "flat" in med:
                     res["empty_launch_us"]["flat_enqueue_us_per_call"] = round(med["flat"] - med["lines"], 3)
+                if "fused" in med:
+                    res["empty_launch_us"]["fused_saves_us_per_call"] = round(med["flat"] - med["fused"], 3)
+                    res["empty_launch_us"]["fusedlines_saves_us_per_call"] = round(med["lines"] - med["fusedlines"], 3)
         return emit(res, all(agree.values()))
     finally:
         for buf in bufs.values():
