@@ -218,12 +218,82 @@ static void test_text_cutting() {
   CHECK(done[0] == 300 && done[1] == 0 && done[2] == 1000);
 }
 
+// Text and slots on both sides of byte 2^32 of the caller's buffers: pieces
+// and slots that touch one another across the line, and one pair past 3 * 2^32.
+static void test_past_4gib() {
+  const uint64_t G = 1ull << 32;
+  std::string why;
+  Pairs p(4);
+  const uint64_t toff[4] = {G - 70, G - 6, G + 64, 3 * G + 5};
+  const uint32_t tlen[4] = {64, 70, 100, 33};
+  const uint64_t ooff[4] = {G - 70, G - 6, G + 64, 3 * G + 5};
+  const uint32_t caps[4] = {64, 70, 75, 24};  // the slots touch across the line too
+  const uint64_t tend = 3 * G + 5 + 33, oend = 3 * G + 5 + 24;
+  auto check = [&](uint64_t text_len, uint64_t out_len, uint64_t n, const uint64_t* oo = nullptr) {
+    return b64_update_check(p.b.data(), p.s.data(), 4, nullptr, text_len, toff, tlen, n, caps, out_len, oo ? oo : ooff,
+                            why);
+  };
+  // bounds exactly at, and one byte short of, the last piece's and the last slot's end
+  CHECK(check(tend, oend, 4) == kNoPiece);
+  CHECK(check(tend - 1, oend, 4) == 3 && has(why, "text outside"));
+  CHECK(check(tend, oend - 1, 4) == 3 && has(why, "slot outside"));
+  // buffers that end at the line, and just past the piece that straddles it
+  CHECK(check(G, oend, 4) == 1 && has(why, "text outside"));
+  CHECK(check(tend, G, 4) == 1 && has(why, "slot outside"));
+  CHECK(check(G + 64, G + 64, 2) == kNoPiece);
+  CHECK(check(G + 63, G + 64, 2) == 1 && check(G + 64, G + 63, 2) == 1);
+  // lengths whose low 32 bits alone would do
+  CHECK(check((uint32_t)tend + 2 * G, oend, 4) == 3 && check(tend, (uint32_t)oend + 2 * G, 4) == 3);
+  // overlap is found across the line, touching is not
+  const uint64_t lap[4] = {G - 70, G - 7, G + 64, 3 * G + 5};
+  CHECK(check(tend, oend, 4, lap) == 1 && has(why, "overlaps"));
+  const uint64_t wrapped[4] = {G - 70, G - 6, G + 64, G - 6 + 3 * G};  // equal to slot 1 mod 2^32 only
+  CHECK(check(tend, 5 * G, 4, wrapped) == kNoPiece);
+
+  // the text's cuts and their staging runs: joined across the line, phases kept
+  const std::vector<std::vector<UpdateCut>> plan = update_launches(toff, tlen, 4, 1 << 20);
+  CHECK(plan.size() == 1 && plan[0].size() == 4);
+  std::vector<Run> runs;
+  std::vector<uint64_t> dev;
+  update_runs(plan[0], runs, dev);
+  CHECK(runs.size() == 2);
+  if (runs.size() == 2) {
+    CHECK(runs[0].src == G - 70 && runs[0].len == 234 && runs[1].src == 3 * G + 5 && runs[1].len == 33);
+    for (size_t k = 0; k < 4; ++k) CHECK(dev[k] % 16 == toff[k] % 16);
+  }
+
+  // places depend on chain positions alone, and the chains are past 2^32 as well
+  const std::vector<uint64_t> decoded = {0, G + 3, 3 * G, 9};
+  const std::vector<uint32_t> ncarry = {0, 1, 2, 3};
+  const std::vector<uint32_t> len(tlen, tlen + 4), cap(caps, caps + 4);
+  std::vector<B64Place> pl;
+  const uint64_t area = b64_update_places(decoded, ncarry, len, cap, pl);
+  CHECK(area < 1024);
+  for (size_t k = 0; k < 4; ++k) {
+    const uint64_t at = std::min<uint64_t>(decoded[k], cap[k]);
+    CHECK(pl[k].slot + at == pl[k].dev && pl[k].dev % 64 == at % 64 && pl[k].room <= cap[k] - at);
+  }
+  CHECK(pl[1].room == 0 && pl[2].room == 0 && pl[0].room == 50 && pl[3].room == 15);
+
+  // copy-back: host positions are 64-bit; runs join across the line when both sides touch
+  b64_update_copyback({0, 64, 140, 320}, {G - 70, G - 6, G + 64, 3 * G + 5}, {64, 70, 75, 24}, runs);
+  CHECK(runs.size() == 3);
+  if (runs.size() == 3) {
+    CHECK(runs[0].src == 0 && runs[0].dst == G - 70 && runs[0].len == 134);  // across the line in one run
+    CHECK(runs[1].src == 140 && runs[1].dst == G + 64 && runs[1].len == 75);  // host side touches, device side does not
+    CHECK(runs[2].src == 320 && runs[2].dst == 3 * G + 5 && runs[2].len == 24);
+  }
+  b64_update_copyback({0, 64}, {G - 64, 2 * G}, {64, 10}, runs);  // host positions equal mod 2^32 do not touch
+  CHECK(runs.size() == 2 && runs[1].dst == 2 * G);
+}
+
 int main() {
   test_refusals();
   test_bound();
   test_places();
   test_copyback();
   test_text_cutting();
+  test_past_4gib();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

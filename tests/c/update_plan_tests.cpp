@@ -165,10 +165,62 @@ static void test_runs() {
   CHECK(runs.size() == 1 && runs[0].len == 136 && dev[1] == dev[0] + 36);
 }
 
+// Sources on both sides of byte 2^32 of the caller's buffer: three pieces that
+// touch one another across the line, and one past 3 * 2^32.  Nothing in the
+// plan may be kept in 32 bits.
+static void test_past_4gib() {
+  const uint64_t G = 1ull << 32;
+  const std::vector<uint64_t> offs = {G - 70, G - 6, G + 64, 3 * G + 5};
+  const std::vector<uint32_t> sizes = {64, 70, 100, 33};
+  const uint64_t end = 3 * G + 5 + 33;
+  std::string why;
+  std::vector<lbf_sha1_state> st = fresh(4);
+  // bounds: exactly at the last piece's end, one byte short of it, and a buffer that ends at the line
+  CHECK(update_check(st.data(), 4, nullptr, end, offs.data(), sizes.data(), 4, why) == kNoPiece);
+  CHECK(update_check(st.data(), 4, nullptr, end - 1, offs.data(), sizes.data(), 4, why) == 3 &&
+        why.find("outside") != std::string::npos);
+  CHECK(update_check(st.data(), 4, nullptr, G, offs.data(), sizes.data(), 4, why) == 1);
+  CHECK(update_check(st.data(), 4, nullptr, G + 64, offs.data(), sizes.data(), 3, why) == 2);
+  CHECK(update_check(st.data(), 4, nullptr, G + 164, offs.data(), sizes.data(), 3, why) == kNoPiece);
+  // a base_len whose low 32 bits are large enough and whose high bits are not
+  CHECK(update_check(st.data(), 4, nullptr, (uint32_t)end + 2 * G, offs.data(), sizes.data(), 4, why) == 3);
+  // one launch, the cuts at the 64-bit offsets
+  check_plan(offs, sizes, 1 << 20, 1);
+  const std::vector<std::vector<UpdateCut>> plan = update_launches(offs.data(), sizes.data(), 4, 1 << 20);
+  CHECK(plan.size() == 1 && plan[0].size() == 4);
+  for (size_t k = 0; k < 4 && k < plan[0].size(); ++k)
+    CHECK(plan[0][k].off == offs[k] && plan[0][k].size == sizes[k] && plan[0][k].last);
+  // a piece cut into launches keeps counting past the line: 64-byte launches from 2^32 - 70
+  const std::vector<std::vector<UpdateCut>> cut = update_launches(offs.data(), sizes.data(), 2, 64);
+  CHECK(cut.size() == 3);
+  if (cut.size() == 3) {
+    CHECK(cut[0].size() == 1 && cut[0][0].off == G - 70 && cut[0][0].size == 64);
+    CHECK(cut[1].size() == 1 && cut[1][0].off == G - 6 && cut[1][0].size == 64 && !cut[1][0].last);
+    CHECK(cut[2].size() == 1 && cut[2][0].off == G + 58 && cut[2][0].size == 6 && cut[2][0].last);
+  }
+  // the runs join across the line; device positions keep the source's phase mod 16
+  std::vector<Run> runs;
+  std::vector<uint64_t> dev;
+  const uint64_t area = update_runs(plan[0], runs, dev);
+  CHECK(runs.size() == 2);
+  if (runs.size() == 2) {
+    CHECK(runs[0].src == G - 70 && runs[0].len == 234 && runs[0].dst % 16 == (G - 70) % 16);
+    CHECK(runs[1].src == 3 * G + 5 && runs[1].len == 33 && runs[1].dst % 16 == 5 && runs[1].dst >= runs[0].dst + 234);
+    CHECK(dev[0] == runs[0].dst && dev[1] == dev[0] + 64 && dev[2] == dev[0] + 134 && dev[3] == runs[1].dst);
+    CHECK(area == runs[1].dst + 33 && area < 512);
+  }
+  for (size_t k = 0; k < 4; ++k) CHECK(dev[k] % 16 == offs[k] % 16);
+  // out of order: a piece below the line after one above it starts a run of its own
+  std::vector<UpdateCut> back = {{0, G + 64, 100, true}, {1, G - 6, 70, true}, {2, G + 164, 8, true}};
+  update_runs(back, runs, dev);
+  CHECK(runs.size() == 3 && runs[1].src == G - 6 && runs[1].dst % 16 == (G - 6) % 16 && runs[2].src == G + 164);
+}
+
 int main() {
   test_refusals();
   test_cutting();
   test_runs();
+  test_past_4gib();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;
