@@ -90,6 +90,16 @@ _SIGS = {
     "lbf_b64_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                         _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_b64_enc_state_init": (None, [_c.c_void_p, _c.c_uint64, _c.c_int]),
+    "lbf_b64_text_length": (_c.c_uint64, [_c.c_uint64, _c.c_int]),
+    "lbf_b64_encode_update_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                                _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                                _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                                _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_b64_encode_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                               _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                               _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_set_b64_lines": (_c.c_int, [_c.c_int]),
     "lbf_ctx_b64_update_stats": (_c.c_int, [_c.c_void_p, _c.POINTER(_c.c_uint64), _c.POINTER(_c.c_uint64)]),
     "lbf_set_b64_flat": (_c.c_int, [_c.c_int]),

@@ -18,6 +18,10 @@ own call sites:
   decoder (base64.h:215-330) in front of that object, fed the pieces of a
   SendChunk payload's text as they arrive (ChunkMethods.cpp:137-167): a
   16-byte decoder state beside each chain's hash state.
+* ``ChunkHasher.update_encode`` with ``new_b64_enc_states`` == the seeder's
+  re-verify and base64 encode (ChunkMethods.cpp:89-135, xmlrpc++'s encoder,
+  base64.h:154-210) fed the pieces of a chunk as they are read: a 16-byte
+  encoder state beside each chain's hash state, text in either peer layout.
 
 All hashing runs on the GPU; there is no CPU path in this module.
 """
@@ -65,6 +69,36 @@ def new_b64_states(n: int) -> np.ndarray:
     if states.size:
         load().lbf_b64_state_init(states.ctypes.data, states.size)
     return states
+
+
+# lbf_b64_enc_state (lbf_hash.h): the base64 encoder stopped between two pieces
+# of a chunk's bytes, 16 bytes, the partner of the chain's STATE_DTYPE record.
+B64_ENC_STATE_DTYPE = np.dtype({"names": ["taken", "carry", "ncarry", "layout", "zero"],
+                                "formats": [np.uint64, np.uint32, np.uint8, np.uint8, np.uint16],
+                                "offsets": [0, 8, 12, 13, 14], "itemsize": 16})
+B64_LAYOUTS = {"xmlrpc": 0, "flat": 1}  # LBF_B64_LAYOUT_*
+
+
+def _layout(layout) -> int:
+    if layout in B64_LAYOUTS:
+        return B64_LAYOUTS[layout]
+    if layout in (0, 1):
+        return int(layout)
+    raise ValueError("layout must be 'xmlrpc' or 'flat'")
+
+
+def new_b64_enc_states(n: int, layout="xmlrpc") -> np.ndarray:
+    """n fresh encoder states of one layout, as lbf_b64_enc_state_init leaves
+    them (host code, no GPU)."""
+    states = np.empty(int(n), dtype=B64_ENC_STATE_DTYPE)
+    if states.size:
+        load().lbf_b64_enc_state_init(states.ctypes.data, states.size, _layout(layout))
+    return states
+
+
+def b64_text_length(size: int, layout="xmlrpc") -> int:
+    """lbf_b64_text_length: characters of the whole text of a chunk of `size` bytes."""
+    return int(load().lbf_b64_text_length(int(size), _layout(layout)))
 
 
 def b64_27(digest: bytes) -> str:
@@ -311,6 +345,63 @@ class ChunkHasher:
                                                  sizes.ctypes.data, None if exp is None else ver.ctypes.data))
         return sizes, ver.astype(bool)
 
+    # -- chunks to send, encoded and hashed piece by piece (lbf_b64_encode_update_batch)
+    def update_encode(self, enc_states, states, data, offsets, sizes, text, text_offsets, text_caps, state_of=None,
+                      final=None, expected=None):
+        """Piece i = data[offsets[i], + sizes[i]) continues chain state_of[i] (chain
+        i without state_of): the pair enc_states[s], states[s] (from
+        new_b64_enc_states / new_states, or restored from bytes), updated in place.
+        Its chunk's text slot is text[text_offsets[i], + text_caps[i]) (`text` a
+        writable uint8 array); the characters the piece produces land there at
+        their place in the chunk's text, and no other byte of `text` is written.
+        Returns (new_offsets, new_lens): where in `text` each piece's new
+        characters lie and how many there are.  With `final`, a piece with
+        final[i] set ends its chain, and the result is (new_offsets, new_lens,
+        text_sizes, verdicts): for a final piece the chunk's text length
+        (text_caps[i] + 1 when it does not fit) and, with `expected`, whether the
+        text fits and the SHA-1 is the chunk's; entries of the other pieces are
+        0 / False."""
+        for st, dt, what in ((enc_states, B64_ENC_STATE_DTYPE, "enc_states"), (states, STATE_DTYPE, "states")):
+            if not (isinstance(st, np.ndarray) and st.dtype == dt and st.ndim == 1 and st.flags.c_contiguous
+                    and st.flags.writeable):
+                raise ValueError(f"{what} must be a writable C-contiguous 1-d array of its state dtype")
+        if enc_states.size != states.size:
+            raise ValueError("enc_states and states differ in length")
+        if not (isinstance(text, np.ndarray) and text.dtype == np.uint8 and text.flags.c_contiguous
+                and text.flags.writeable):
+            raise ValueError("text must be a writable C-contiguous uint8 array")
+        buf = _as_u8(data)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        szs = np.ascontiguousarray(sizes, dtype=np.uint32)
+        toff = np.ascontiguousarray(text_offsets, dtype=np.uint64)
+        caps = np.ascontiguousarray(text_caps, dtype=np.uint32)
+        n = offs.size
+        if not (szs.size == toff.size == caps.size == n):
+            raise ValueError("offsets, sizes, text_offsets and text_caps differ in length")
+        so = None if state_of is None else np.ascontiguousarray(state_of, dtype=np.uint32)
+        fin = None if final is None else np.ascontiguousarray(final).astype(bool).astype(np.uint8)
+        exp = None if expected is None else np.ascontiguousarray(expected, dtype=np.uint8).reshape(-1, DIGEST)
+        for a, what in ((so, "state_of"), (fin, "final"), (exp, "expected")):
+            if a is not None and a.shape[0] != n:
+                raise ValueError(f"{what} differs in length")
+        new_off = np.zeros(n, dtype=np.uint64)
+        new_len = np.zeros(n, dtype=np.uint32)
+        tsizes = np.zeros(n, dtype=np.uint32)
+        ver = np.zeros(n, dtype=np.uint8)
+        if n:
+            base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
+            ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+            check(self._lib.lbf_b64_encode_update_batch(self._h, enc_states.ctypes.data, states.ctypes.data,
+                                                        enc_states.size, ptr(so), base, buf.size, offs.ctypes.data,
+                                                        szs.ctypes.data, ptr(fin), n, ptr(exp),
+                                                        None if exp is None else ver.ctypes.data,
+                                                        text.ctypes.data if text.size else None, text.size,
+                                                        toff.ctypes.data, caps.ctypes.data, new_off.ctypes.data,
+                                                        new_len.ctypes.data, tsizes.ctypes.data))
+        if final is None:
+            return new_off, new_len
+        return new_off, new_len, tsizes, ver.astype(bool)
+
     # -- chunks read straight from a file (lbf_file_ranges) ---------------------
     def hash_file(self, path: str, offsets, sizes) -> np.ndarray:
         """Digests of byte ranges of a file, pread into pinned staging: EncodeFile's
@@ -536,6 +627,20 @@ def b64_update_launch(b64_states, sha_states, n_states, state_of, text, text_off
                                        p(digests), p(expected), p(verdicts), p(piece_offsets), p(piece_sizes), stream))
 
 
+def b64_encode_update_launch(enc_states, sha_states, n_states, state_of, base, offsets, sizes, final, n, text,
+                             text_offsets, text_caps, new_offsets, new_lens, text_sizes, digests, expected, verdicts,
+                             stream=None):
+    """lbf_b64_encode_update_launch: pieces of bytes in device memory encoded into
+    their chunks' text slots and absorbed into device-resident state pairs,
+    asynchronous on `stream`; state_of, final, digests and expected/verdicts may
+    be None."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_b64_encode_update_launch(p(enc_states), p(sha_states), n_states, p(state_of), p(base),
+                                              p(offsets), p(sizes), p(final), n, p(text), p(text_offsets),
+                                              p(text_caps), p(new_offsets), p(new_lens), p(text_sizes), p(digests),
+                                              p(expected), p(verdicts), stream))
+
+
 def set_b64_lines(on) -> bool:
     """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
     off, process-wide; returns the previous setting."""
@@ -567,5 +672,6 @@ def set_kernel_variant(v: int):
 
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
-           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "B64_ENC_STATE_DTYPE", "new_b64_enc_states",
+           "b64_text_length", "b64_encode_update_launch", "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -442,6 +442,103 @@ int lbf_b64_update_batch(lbf_ctx* ctx, lbf_b64_state* b64_states, lbf_sha1_state
                          uint64_t n, const uint32_t* expected_sizes, const uint8_t* expected, uint8_t* out,
                          uint64_t out_len, const uint64_t* out_offsets, uint32_t* out_sizes, uint8_t* verdicts);
 
+/* ---- resumable base64 encode beside the resumable SHA-1 --------------------
+ * The seeder's side of the same wire (ChunkMethods.cpp:89-135: re-verify, then
+ * base64-encode the payload), for a chunk that is read or held in pieces: the
+ * mirror image of lbf_b64_state.  A lbf_b64_enc_state is the encoder stopped
+ * between two pieces: 16 bytes, owned by the caller, copyable, kept beside the
+ * chain's lbf_sha1_state at the same index of a parallel array.  Two layouts:
+ * xmlrpc++'s lines (base64.h:154-210 as the frame sends them: 72 characters and
+ * a space) and the unbroken RFC 4648 text bitflood's Java and Perl peers write
+ * (XMLEnvelopeProcessor.java:124, RPC/XML.pm:638).  With P(G) the text position
+ * of group G -- 4G + G/18 in lines, 4G unbroken -- a piece of s bytes on a chain
+ * that has taken t writes the characters [P(t/3), P((t+s)/3)) of the chunk's
+ * text and nothing else (in lines, so, the piece that completes a line's 18th
+ * group writes the separator behind it); the (t+s) % 3 bytes left over are
+ * carried; a final piece also writes the last group ("xx==" / "xxx=") of a
+ * chunk whose size is no multiple of 3, and puts the record back to taken = 0,
+ * ncarry = 0, carry = 0 with the layout kept.  However a chunk is cut into
+ * pieces, its slot ends up holding the whole chunk's text, lbf_b64_text_length
+ * characters.  Invariants (the batch call checks them; the launch masks and
+ * clamps): ncarry == taken % 3, carry < 2^(8*ncarry), layout <= 1, zero == 0,
+ * taken < 2^61, and the partner SHA state's total == taken.  The two functions
+ * below are host code and need no GPU. */
+#define LBF_B64_LAYOUT_XMLRPC 0   /* 72 characters + one separator (a space) per line */
+#define LBF_B64_LAYOUT_FLAT   1   /* unbroken RFC 4648 text */
+typedef struct lbf_b64_enc_state {
+  uint64_t taken;   /* bytes of the chunk encoded or carried so far */
+  uint32_t carry;   /* the bytes of the unfinished group: byte k at bits [8k, 8k+8) */
+  uint8_t  ncarry;  /* 0..2 */
+  uint8_t  layout;  /* LBF_B64_LAYOUT_* ; survives the reset after a final piece */
+  uint16_t zero;
+} lbf_b64_enc_state;
+/* Any layout but LBF_B64_LAYOUT_FLAT gives LBF_B64_LAYOUT_XMLRPC. */
+void lbf_b64_enc_state_init(lbf_b64_enc_state* states, uint64_t n, int layout);
+/* Length of a chunk's whole text: lbf_b64_put_length(size) in lines,
+ * 4 * ceil(size / 3) unbroken. */
+uint64_t lbf_b64_text_length(uint64_t size, int layout);
+
+/* Device-resident and asynchronous on `stream`: three enqueues -- a small
+ * kernel that gives the hash its piece sizes (in d_new_lens, which the last
+ * kernel then overwrites), lbf_sha1_update_launch unchanged, and the encode
+ * kernel, which runs behind the hash and clears an overflowed final piece's
+ * verdict itself -- no host round trip, no device allocation.  Piece i =
+ * d_base[d_offsets[i], + d_sizes[i]) continues chain d_state_of[i] (chain i
+ * when d_state_of is NULL): the pair d_enc_states[s], d_sha_states[s] of
+ * n_states pairs (both arrays 16-byte aligned).  Its chunk's text slot is
+ * d_text[d_text_offsets[i], + d_text_caps[i]) -- repeated for every piece of
+ * the chain -- and the characters the piece produces land in it at their place
+ * in the chunk's text; no byte at or past the cap is written, and no byte of
+ * the slot other than those characters, so slots may be packed next to one
+ * another at any byte phase.  d_new_offsets[i] is where the new characters lie
+ * in d_text (d_text_offsets[i] + their position in the chunk's text, clipped
+ * to the cap) and d_new_lens[i] how many were written (clipped at the cap): a
+ * streaming seeder sends exactly those.  A piece with d_final[i] != 0 ends its
+ * chain: d_text_sizes[i] = the chunk's text length, or d_text_caps[i] + 1 when
+ * the text does not fit, in which case d_verdicts[i] is cleared; digest and/or
+ * verdict as lbf_sha1_update_launch writes them; both records restart (the
+ * layout is kept).  Entries of d_text_sizes, d_digests and d_verdicts of pieces
+ * that are not final are left untouched.  d_text_sizes is required; d_final,
+ * d_digests and d_expected / d_verdicts may be NULL as for
+ * lbf_sha1_update_launch.  The layout is read per piece from the record, so
+ * both may share a launch.  A piece whose state index is >= n_states is
+ * skipped, nothing read or written for it; one whose cap exceeds
+ * lbf_b64_text_length(1 GiB, LBF_B64_LAYOUT_XMLRPC) encodes nothing, hands the
+ * hash an empty piece, gets d_new_lens[i] = 0 and, when final, verdict 0 and
+ * d_text_sizes[i] = 0 with both records restarted.  A forged record (ncarry is
+ * taken from `taken` % 3, carry masked to it, layout & 1, taken clamped below
+ * 2^61) can never make the kernel write outside its slot, its two records or
+ * its table entries.  Two pieces of one chain in one launch are undefined as
+ * for lbf_sha1_update_launch.  Every array is checked against its allocation
+ * and its element alignment. */
+int lbf_b64_encode_update_launch(lbf_b64_enc_state* d_enc_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
+                                 const uint32_t* d_state_of, const uint8_t* d_base, const uint64_t* d_offsets,
+                                 const uint32_t* d_sizes, const uint8_t* d_final, uint64_t n, char* d_text,
+                                 const uint64_t* d_text_offsets, const uint32_t* d_text_caps,
+                                 uint64_t* d_new_offsets, uint32_t* d_new_lens, uint32_t* d_text_sizes,
+                                 uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts, void* stream);
+/* The same over host memory, synchronous on the context's first device.  Piece
+ * i = data[offsets[i], + sizes[i]) of chain state_of[i], whose chunk's text
+ * slot is text[text_offsets[i], + text_caps[i]).  Checked before any GPU work,
+ * each refused with LBF_ERR_INVALID and a message naming the piece, states and
+ * outputs untouched: a piece outside [data, data + data_len); a slot outside
+ * [text, text + text_len); a state index out of range; two pieces of one
+ * state; a broken invariant of either record; a chunk over 1 GiB (taken +
+ * size) or a cap the launch would refuse; slots of different states that
+ * overlap.  At most LBF_UPDATE_MB MiB of piece bytes go to the device per
+ * launch (a larger piece is cut where lbf_sha1_update_batch cuts it and fed
+ * over successive launches).  What comes back: only the characters this call
+ * produced, one copy per run of touching ranges -- no other byte of `text` is
+ * written -- the states, new_offsets[i] / new_lens[i] (either may be NULL; the
+ * offsets are positions in `text`), and for final pieces text_sizes[i] (may be
+ * NULL) and verdicts[i].  expected and verdicts go together and may be NULL. */
+int lbf_b64_encode_update_batch(lbf_ctx* ctx, lbf_b64_enc_state* enc_states, lbf_sha1_state* sha_states,
+                                uint64_t n_states, const uint32_t* state_of, const uint8_t* data, uint64_t data_len,
+                                const uint64_t* offsets, const uint32_t* sizes, const uint8_t* final_flags,
+                                uint64_t n, const uint8_t* expected, uint8_t* verdicts, char* text,
+                                uint64_t text_len, const uint64_t* text_offsets, const uint32_t* text_caps,
+                                uint64_t* new_offsets, uint32_t* new_lens, uint32_t* text_sizes);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */
