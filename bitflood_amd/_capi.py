@@ -82,6 +82,12 @@ _SIGS = {
     "lbf_sha1_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                          _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_sha1_update_seq_launch": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                              _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_sha1_update_seq_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                             _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                             _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_b64_state_init": (None, [_c.c_void_p, _c.c_uint64]),
     "lbf_b64_update_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
@@ -90,6 +96,15 @@ _SIGS = {
     "lbf_b64_update_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                         _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
                                         _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_b64_update_seq_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                             _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                             _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                             _c.c_void_p]),
+    "lbf_b64_update_seq_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                            _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                            _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,
+                                            _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_b64_enc_state_init": (None, [_c.c_void_p, _c.c_uint64, _c.c_int]),
     "lbf_b64_text_length": (_c.c_uint64, [_c.c_uint64, _c.c_int]),
     "lbf_b64_encode_update_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,

@@ -130,6 +130,29 @@ def chunk_table(length: int, chunk_size: int, base_offset: int = 0):
     return offs + np.uint64(base_offset), sizes
 
 
+def chain_table(state_of):
+    """The chain table the *_seq_launch calls read, from the state each piece
+    names: (order, chain_state, chain_first).  A stable grouping: chains stand
+    in the order their first pieces stand in `state_of`, and a chain's pieces
+    keep their order.  order[j] is the caller's piece at table position j (lay
+    the per-piece arrays out as arr[order]; results at position j belong to
+    piece order[j]), chain c continues state chain_state[c], and its pieces are
+    table positions [chain_first[c], chain_first[c + 1]).  When no state repeats
+    order is the identity and chain_state equals state_of."""
+    so = np.ascontiguousarray(state_of, dtype=np.uint32).reshape(-1)
+    if so.size == 0:
+        return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(1, dtype=np.uint32)
+    states, first_at, chain_of = np.unique(so, return_index=True, return_inverse=True)
+    by_first = np.argsort(first_at, kind="stable")  # chains in the order of their first pieces
+    rank = np.empty(by_first.size, dtype=np.int64)
+    rank[by_first] = np.arange(by_first.size)
+    chain = rank[chain_of.reshape(-1)]
+    order = np.argsort(chain, kind="stable").astype(np.uint32)
+    chain_first = np.zeros(by_first.size + 1, dtype=np.uint32)
+    chain_first[1:] = np.cumsum(np.bincount(chain, minlength=by_first.size))
+    return order, states[by_first].astype(np.uint32), chain_first
+
+
 def _as_u8(data) -> np.ndarray:
     if isinstance(data, np.ndarray):
         return np.ascontiguousarray(data).view(np.uint8).reshape(-1)
@@ -271,6 +294,20 @@ class ChunkHasher:
         row i of the (n, 20) result and its state is fresh again; rows of the
         other pieces are zero.  With `expected` the result is the bool verdicts
         instead (False for pieces that are not final)."""
+        return self._update_chunks(self._lib.lbf_sha1_update_batch, states, data, offsets, sizes, state_of, final,
+                                   expected)
+
+    def update_chunks_seq(self, states, data, offsets, sizes, state_of=None, final=None, expected=None) -> np.ndarray:
+        """update_chunks without "at most one piece per state" (lbf_sha1_update_seq_batch):
+        pieces that name one state are absorbed in the order they stand in the
+        call, each touched state travels once per launch, and the results are
+        at the caller's piece indices.  A final piece must be the last piece of
+        its state in the call.  A call in which no state repeats returns what
+        update_chunks returns."""
+        return self._update_chunks(self._lib.lbf_sha1_update_seq_batch, states, data, offsets, sizes, state_of, final,
+                                   expected)
+
+    def _update_chunks(self, call, states, data, offsets, sizes, state_of, final, expected) -> np.ndarray:
         if not (isinstance(states, np.ndarray) and states.dtype == STATE_DTYPE and states.ndim == 1
                 and states.flags.c_contiguous and states.flags.writeable):
             raise ValueError("states must be a writable C-contiguous 1-d array of STATE_DTYPE")
@@ -291,10 +328,9 @@ class ChunkHasher:
         if n:
             base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
             ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-            check(self._lib.lbf_sha1_update_batch(self._h, states.ctypes.data, states.size, ptr(so), base, buf.size,
-                                                  offs.ctypes.data, szs.ctypes.data, ptr(fin), n,
-                                                  None if exp is not None else out.ctypes.data, ptr(exp),
-                                                  None if exp is None else ver.ctypes.data))
+            check(call(self._h, states.ctypes.data, states.size, ptr(so), base, buf.size, offs.ctypes.data,
+                       szs.ctypes.data, ptr(fin), n, None if exp is not None else out.ctypes.data, ptr(exp),
+                       None if exp is None else ver.ctypes.data))
         return out if exp is None else ver.astype(bool)
 
     # -- chunks' base64 text decoded and hashed piece by piece (lbf_b64_update_batch)
@@ -310,6 +346,22 @@ class ChunkHasher:
         piece the decoded length (expected_sizes[i] + 1 when more) and, with
         `expected`, whether length and SHA-1 are the chunk's; entries of the other
         pieces are 0 / False."""
+        return self._update_text(self._lib.lbf_b64_update_batch, b64_states, sha_states, text, text_offsets,
+                                 text_lens, out, out_offsets, expected_sizes, state_of, final, expected)
+
+    def update_text_seq(self, b64_states, sha_states, text, text_offsets, text_lens, out, out_offsets, expected_sizes,
+                        state_of=None, final=None, expected=None):
+        """update_text without "at most one piece per state" (lbf_b64_update_seq_batch):
+        pieces that name one chain -- the frames of one chunk a receiver holds
+        when it drains its sockets -- are decoded and absorbed in the order they
+        stand in the call; they repeat the chain's slot and chunk size.  A final
+        piece must be the last piece of its chain in the call.  A call in which
+        no chain repeats returns what update_text returns."""
+        return self._update_text(self._lib.lbf_b64_update_seq_batch, b64_states, sha_states, text, text_offsets,
+                                 text_lens, out, out_offsets, expected_sizes, state_of, final, expected)
+
+    def _update_text(self, call, b64_states, sha_states, text, text_offsets, text_lens, out, out_offsets,
+                     expected_sizes, state_of, final, expected):
         for st, dt, what in ((b64_states, B64_STATE_DTYPE, "b64_states"), (sha_states, STATE_DTYPE, "sha_states")):
             if not (isinstance(st, np.ndarray) and st.dtype == dt and st.ndim == 1 and st.flags.c_contiguous
                     and st.flags.writeable):
@@ -338,11 +390,10 @@ class ChunkHasher:
         if n:
             base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
             ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
-            check(self._lib.lbf_b64_update_batch(self._h, b64_states.ctypes.data, sha_states.ctypes.data,
-                                                 b64_states.size, ptr(so), base, buf.size, toff.ctypes.data,
-                                                 tlen.ctypes.data, ptr(fin), n, esz.ctypes.data, ptr(exp),
-                                                 out.ctypes.data if out.size else None, out.size, ooff.ctypes.data,
-                                                 sizes.ctypes.data, None if exp is None else ver.ctypes.data))
+            check(call(self._h, b64_states.ctypes.data, sha_states.ctypes.data, b64_states.size, ptr(so), base,
+                       buf.size, toff.ctypes.data, tlen.ctypes.data, ptr(fin), n, esz.ctypes.data, ptr(exp),
+                       out.ctypes.data if out.size else None, out.size, ooff.ctypes.data, sizes.ctypes.data,
+                       None if exp is None else ver.ctypes.data))
         return sizes, ver.astype(bool)
 
     # -- chunks to send, encoded and hashed piece by piece (lbf_b64_encode_update_batch)
@@ -615,6 +666,29 @@ def update_launch(states, n_states, state_of, base, offsets, sizes, final, n, di
                                         p(digests), p(expected), p(verdicts), stream))
 
 
+def update_seq_launch(states, n_states, chain_state, chain_first, n_chains, base, offsets, sizes, final, n, digests,
+                      expected=None, verdicts=None, stream=None):
+    """lbf_sha1_update_seq_launch: update_launch with several pieces per chain,
+    absorbed in table order; chain_state / chain_first are the chain table
+    (chain_table), chain_state may be None (chain c continues state c)."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_sha1_update_seq_launch(p(states), n_states, p(chain_state), p(chain_first), n_chains, p(base),
+                                            p(offsets), p(sizes), p(final), n, p(digests), p(expected), p(verdicts),
+                                            stream))
+
+
+def b64_update_seq_launch(b64_states, sha_states, n_states, chain_state, chain_first, n_chains, text, text_offsets,
+                          text_lens, final, n, out, out_offsets, caps, out_sizes, digests, expected, verdicts,
+                          piece_offsets, piece_sizes, stream=None):
+    """lbf_b64_update_seq_launch: b64_update_launch with several pieces per chain,
+    decoded and absorbed in table order, in three enqueues whatever their number."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_b64_update_seq_launch(p(b64_states), p(sha_states), n_states, p(chain_state), p(chain_first),
+                                           n_chains, p(text), p(text_offsets), p(text_lens), p(final), n, p(out),
+                                           p(out_offsets), p(caps), p(out_sizes), p(digests), p(expected), p(verdicts),
+                                           p(piece_offsets), p(piece_sizes), stream))
+
+
 def b64_update_launch(b64_states, sha_states, n_states, state_of, text, text_offsets, text_lens, final, n, out,
                       out_offsets, caps, out_sizes, digests, expected, verdicts, piece_offsets, piece_sizes,
                       stream=None):
@@ -673,5 +747,6 @@ def set_kernel_variant(v: int):
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
            "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "B64_ENC_STATE_DTYPE", "new_b64_enc_states",
-           "b64_text_length", "b64_encode_update_launch", "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
+           "b64_text_length", "b64_encode_update_launch", "chain_table", "update_seq_launch", "b64_update_seq_launch",
+           "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -2,7 +2,9 @@
 // fed through lbf_sha1_update_batch, one GPU call per Update(), and per-slot
 // base64 decoder states beside them fed through lbf_b64_update_batch, one GPU
 // call per UpdateText(), and per-slot base64 encoder states fed through
-// lbf_b64_encode_update_batch, one GPU call per UpdateEncode().
+// lbf_b64_encode_update_batch, one GPU call per UpdateEncode().  UpdateSeq() and
+// UpdateTextSeq() are Update() and UpdateText() through lbf_sha1_update_seq_batch
+// and lbf_b64_update_seq_batch: several pieces per slot, in the caller's order.
 #include "libBitFlood/PieceHasher.H"
 
 #include "lbf_hash.h"
@@ -30,6 +32,16 @@ std::shared_ptr<lbf_ctx> PieceHasher::Ctx() const {
 
 Error::ErrorCode PieceHasher::Update(const U8* i_arena, U64 i_arena_len, const V_Piece& i_pieces,
                                      V_String& o_hashes) {
+  return UpdateBy(false, i_arena, i_arena_len, i_pieces, o_hashes);
+}
+
+Error::ErrorCode PieceHasher::UpdateSeq(const U8* i_arena, U64 i_arena_len, const V_Piece& i_pieces,
+                                        V_String& o_hashes) {
+  return UpdateBy(true, i_arena, i_arena_len, i_pieces, o_hashes);
+}
+
+Error::ErrorCode PieceHasher::UpdateBy(bool i_seq, const U8* i_arena, U64 i_arena_len, const V_Piece& i_pieces,
+                                       V_String& o_hashes) {
   const U64 n = i_pieces.size();
   o_hashes.assign(n, std::string());
   if (n == 0) return Error::NO_ERROR_LBF;
@@ -45,9 +57,9 @@ Error::ErrorCode PieceHasher::Update(const U8* i_arena, U64 i_arena_len, const V
     last[k] = i_pieces[k].m_last ? 1 : 0;
   }
   static const U8 kEmpty = 0;  // an empty arena still gets a real address
-  if (lbf_sha1_update_batch(held.get(), m_states.get(), m_slots, slot.data(), i_arena ? i_arena : &kEmpty,
-                            i_arena ? i_arena_len : 0, offs.data(), sizes.data(), last.data(), n, digests.data(),
-                            nullptr, nullptr) != LBF_OK)
+  const auto call = i_seq ? lbf_sha1_update_seq_batch : lbf_sha1_update_batch;
+  if (call(held.get(), m_states.get(), m_slots, slot.data(), i_arena ? i_arena : &kEmpty, i_arena ? i_arena_len : 0,
+           offs.data(), sizes.data(), last.data(), n, digests.data(), nullptr, nullptr) != LBF_OK)
     return Error::UNKNOWN_ERROR_LBF;
   for (U64 k = 0; k < n; ++k) {
     if (!last[k]) continue;
@@ -61,6 +73,21 @@ Error::ErrorCode PieceHasher::Update(const U8* i_arena, U64 i_arena_len, const V
 Error::ErrorCode PieceHasher::UpdateText(const char* i_text, U64 i_text_len, const V_TextPiece& i_pieces,
                                          U8* io_arena, U64 i_arena_len, const V_String& i_expected_hashes,
                                          std::vector<U8>& o_verdicts, std::vector<U32>* o_sizes) {
+  return UpdateTextBy(false, i_text, i_text_len, i_pieces, io_arena, i_arena_len, i_expected_hashes, o_verdicts,
+                      o_sizes);
+}
+
+Error::ErrorCode PieceHasher::UpdateTextSeq(const char* i_text, U64 i_text_len, const V_TextPiece& i_pieces,
+                                            U8* io_arena, U64 i_arena_len, const V_String& i_expected_hashes,
+                                            std::vector<U8>& o_verdicts, std::vector<U32>* o_sizes) {
+  return UpdateTextBy(true, i_text, i_text_len, i_pieces, io_arena, i_arena_len, i_expected_hashes, o_verdicts,
+                      o_sizes);
+}
+
+Error::ErrorCode PieceHasher::UpdateTextBy(bool i_seq, const char* i_text, U64 i_text_len,
+                                           const V_TextPiece& i_pieces, U8* io_arena, U64 i_arena_len,
+                                           const V_String& i_expected_hashes, std::vector<U8>& o_verdicts,
+                                           std::vector<U32>* o_sizes) {
   const U64 n = i_pieces.size();
   o_verdicts.assign(n, 0);
   if (o_sizes) o_sizes->assign(n, 0);
@@ -85,10 +112,10 @@ Error::ErrorCode PieceHasher::UpdateText(const char* i_text, U64 i_text_len, con
       return Error::UNKNOWN_ERROR_LBF;
   }
   static const char kNoText = 0;  // empty text still gets a real address
-  if (lbf_b64_update_batch(held.get(), m_text_states.get(), m_states.get(), m_slots, slot.data(),
-                           i_text ? i_text : &kNoText, i_text ? i_text_len : 0, toffs.data(), lens.data(),
-                           last.data(), n, caps.data(), expected.data(), io_arena, io_arena ? i_arena_len : 0,
-                           ooffs.data(), sizes.data(), o_verdicts.data()) != LBF_OK)
+  const auto call = i_seq ? lbf_b64_update_seq_batch : lbf_b64_update_batch;
+  if (call(held.get(), m_text_states.get(), m_states.get(), m_slots, slot.data(), i_text ? i_text : &kNoText,
+           i_text ? i_text_len : 0, toffs.data(), lens.data(), last.data(), n, caps.data(), expected.data(), io_arena,
+           io_arena ? i_arena_len : 0, ooffs.data(), sizes.data(), o_verdicts.data()) != LBF_OK)
     return Error::UNKNOWN_ERROR_LBF;
   for (U64 k = 0; k < n; ++k)
     if (!last[k]) o_verdicts[k] = 0;

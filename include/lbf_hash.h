@@ -275,8 +275,8 @@ void lbf_sha1_state_init(lbf_sha1_state* states, uint64_t n);
  * and `buffered` is taken & 63, so a corrupt record can never make the kernel
  * write outside its own 96 bytes.  Two pieces naming ONE state in one launch
  * is undefined here: memory-safe, but the order they are absorbed in is not
- * defined (feed a chain's pieces in successive launches, or use the batch call
- * below, which refuses it).  The arrays are checked against their allocations
+ * defined (feed a chain's pieces in successive launches, or in one launch of
+ * lbf_sha1_update_seq_launch below; the batch call refuses it).  The arrays are checked against their allocations
  * as in lbf_sha1_launch. */
 int lbf_sha1_update_launch(lbf_sha1_state* d_states, uint64_t n_states, const uint32_t* d_state_of,
                            const uint8_t* d_base, const uint64_t* d_offsets, const uint32_t* d_sizes,
@@ -301,6 +301,47 @@ int lbf_sha1_update_batch(lbf_ctx* ctx, lbf_sha1_state* states, uint64_t n_state
                           const uint8_t* base, uint64_t base_len, const uint64_t* offsets,
                           const uint32_t* sizes, const uint8_t* final_flags, uint64_t n,
                           uint8_t* out_digests, const uint8_t* expected, uint8_t* verdicts);
+
+/* Several pieces of one chain in one launch, absorbed in order.  The pieces are
+ * described per piece exactly as for lbf_sha1_update_launch (offsets, sizes,
+ * final flags; outputs indexed by piece); which pieces belong to which chain is
+ * said by a chain table, CSR style, in place of d_state_of: chain c continues
+ * state d_chain_state[c] (state c when d_chain_state is NULL) and its pieces
+ * are the piece indices [d_chain_first[c], d_chain_first[c + 1]), absorbed in
+ * index order (d_chain_first has n_chains + 1 entries).  One lane per chain
+ * holds the record's header in registers from the chain's first piece to its
+ * last and writes it once.  A final piece that is not its chain's last piece
+ * in the launch is defined HERE (the host call below refuses it): it ends the
+ * chunk and writes its outputs, and the pieces behind it begin a new chunk
+ * from the initial value -- what successive launches give.  Against a forged
+ * table: both ends of a chain's range are clamped to n and an inverted range
+ * is empty; a chain whose state index is >= n_states is skipped whole, nothing
+ * read or written for it; pieces that no chain names are left alone; a chain
+ * of no pieces leaves its record as it is.  Two chains naming ONE state, or
+ * one piece named by two chains, stay undefined but memory-safe.  Device-
+ * resident and asynchronous on `stream`, one enqueue; the arrays are checked
+ * against their allocations as in lbf_sha1_update_launch. */
+int lbf_sha1_update_seq_launch(lbf_sha1_state* d_states, uint64_t n_states, const uint32_t* d_chain_state,
+                               const uint32_t* d_chain_first, uint64_t n_chains, const uint8_t* d_base,
+                               const uint64_t* d_offsets, const uint32_t* d_sizes, const uint8_t* d_final,
+                               uint64_t n, uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
+                               void* stream);
+/* lbf_sha1_update_batch without "two pieces of one state": pieces of one state
+ * are absorbed in the order they stand in the call, and results come back at
+ * the caller's piece indices.  Per launch each touched state travels once,
+ * whatever the number of its pieces.  Checked before any GPU work, each refused
+ * with LBF_ERR_INVALID and a message naming the piece, states and outputs
+ * untouched: everything lbf_sha1_update_batch refuses but that; a state's total
+ * plus the SUM of its pieces' sizes past 2^61 bytes; a final piece that is
+ * followed by another piece of its state in the same call (feed the next
+ * chunk's pieces in the next call).  A call in which no state repeats returns
+ * exactly what lbf_sha1_update_batch returns.  Launches are cut by
+ * LBF_UPDATE_MB in caller order as there, so a chain's pieces may straddle
+ * launches, which are ordered. */
+int lbf_sha1_update_seq_batch(lbf_ctx* ctx, lbf_sha1_state* states, uint64_t n_states, const uint32_t* state_of,
+                              const uint8_t* base, uint64_t base_len, const uint64_t* offsets,
+                              const uint32_t* sizes, const uint8_t* final_flags, uint64_t n,
+                              uint8_t* out_digests, const uint8_t* expected, uint8_t* verdicts);
 
 /* ---- resumable base64 decode chained to the resumable SHA-1 ----------------
  * A SendChunk payload is base64 text (ChunkMethods.cpp:137-167) and reaches a
@@ -441,6 +482,54 @@ int lbf_b64_update_batch(lbf_ctx* ctx, lbf_b64_state* b64_states, lbf_sha1_state
                          const uint64_t* text_offsets, const uint32_t* text_lens, const uint8_t* final_flags,
                          uint64_t n, const uint32_t* expected_sizes, const uint8_t* expected, uint8_t* out,
                          uint64_t out_len, const uint64_t* out_offsets, uint32_t* out_sizes, uint8_t* verdicts);
+
+/* Several pieces of one chain's text in one launch, decoded and absorbed in
+ * order: lbf_b64_update_launch's arrays per piece (the caller still repeats
+ * slot start and chunk size for every piece of a chain), and the chain table
+ * of lbf_sha1_update_seq_launch in place of d_state_of, naming state PAIRS.
+ * Three enqueues whatever the piece count and whatever lbf_set_b64_fused says:
+ * a decode kernel with one workgroup per chain, which reads the decoder's
+ * record once, runs the line path's, the flat path's and the general rule's
+ * stages on each piece in turn (lbf_set_b64_lines / lbf_set_b64_flat say which
+ * stages run in front of the general rule, as on the fused route) and writes
+ * the record once behind the last piece; lbf_sha1_update_seq_launch over the
+ * work arrays with the same table; and the length check of final pieces.
+ * Bytes, d_out_sizes, verdicts and the work arrays, each at the piece's index,
+ * and both records are what the same pieces give when fed one per launch
+ * through lbf_b64_update_launch.  A final piece that is not its chain's last
+ * is defined here as for lbf_sha1_update_seq_launch: both records restart and
+ * the pieces behind it begin a new chunk (the host call below refuses it).
+ * That chunk's pieces must name a slot that does not overlap the ended
+ * chunk's: the hash runs behind the decode of the whole launch and reads each
+ * piece's bytes from its slot.  A
+ * piece whose d_caps[i] exceeds 1 GiB is passed over as lbf_b64_update_launch
+ * passes it over, and the chain goes on with the next piece.  The forged-table
+ * rules are those of lbf_sha1_update_seq_launch; every array is checked
+ * against its allocation. */
+int lbf_b64_update_seq_launch(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
+                              const uint32_t* d_chain_state, const uint32_t* d_chain_first, uint64_t n_chains,
+                              const char* d_text, const uint64_t* d_text_offsets, const uint32_t* d_text_lens,
+                              const uint8_t* d_final, uint64_t n, uint8_t* d_out, const uint64_t* d_out_offsets,
+                              const uint32_t* d_caps, uint32_t* d_out_sizes, uint8_t* d_digests,
+                              const uint8_t* d_expected, uint8_t* d_verdicts, uint64_t* d_piece_offsets,
+                              uint32_t* d_piece_sizes, void* stream);
+/* lbf_b64_update_batch without "two pieces of one state": pieces of one state
+ * are decoded and absorbed in the order they stand in the call, and results
+ * come back at the caller's piece indices.  Per launch a touched state pair
+ * travels once and a chain's decoded bytes come back as one range.  Checked
+ * before any GPU work, each refused with LBF_ERR_INVALID and a message naming
+ * the piece, states and outputs untouched: everything lbf_b64_update_batch
+ * refuses but that (the invariants against each pair as it stands at the call;
+ * overlap among the slots of different states); pieces of one state that name
+ * different slots or chunk sizes; a final piece that is followed by another
+ * piece of its state in the same call.  A call in which no state repeats
+ * returns exactly what lbf_b64_update_batch returns, and the calls count in
+ * lbf_ctx_b64_update_stats / lbf_ctx_b64_flat_stats as its calls do. */
+int lbf_b64_update_seq_batch(lbf_ctx* ctx, lbf_b64_state* b64_states, lbf_sha1_state* sha_states, uint64_t n_states,
+                             const uint32_t* state_of, const char* text, uint64_t text_len,
+                             const uint64_t* text_offsets, const uint32_t* text_lens, const uint8_t* final_flags,
+                             uint64_t n, const uint32_t* expected_sizes, const uint8_t* expected, uint8_t* out,
+                             uint64_t out_len, const uint64_t* out_offsets, uint32_t* out_sizes, uint8_t* verdicts);
 
 /* ---- resumable base64 encode beside the resumable SHA-1 --------------------
  * The seeder's side of the same wire (ChunkMethods.cpp:89-135: re-verify, then
