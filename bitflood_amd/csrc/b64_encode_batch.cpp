@@ -2,8 +2,9 @@
 // memory encoded into the chunks' text slots and absorbed into caller-owned
 // resumable state pairs (lbf_b64_enc_state, lbf_sha1_state), synchronously on
 // worker 0's first stream.  What is refused, which characters a cut writes,
-// where they lie on the device and how they come back is b64_encode_plan.hpp;
-// the pieces are cut into launches and packed into copies by update_plan.hpp.
+// where they and the launch's tables lie on the device is b64_encode_plan.hpp;
+// the pieces are cut into launches and packed into copies by update_plan.hpp;
+// how a call begins and how characters come back is update_host.hpp.
 // Here the plan meets the stream: per launch one H2D per run of adjacent
 // pieces, one of the touched state pairs and tables,
 // lbf_b64_encode_update_launch, the tables back, then only the characters the
@@ -14,19 +15,11 @@
 #include <algorithm>
 
 #include "b64_encode_plan.hpp"
-#include "lbf_host.hpp"
+#include "update_host.hpp"
 
 using namespace lbf;
 
 namespace {
-
-uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
-// The call's device memory: the update calls' one allocation on worker 0's
-// device (current when this runs), grown on demand; the caller holds ctx->mu.
-int encode_scratch(lbf_ctx* ctx, uint64_t need) {
-  return grow_scratch(ctx->upd_dev, ctx->upd_cap, need, up(need, 1ull << 20), "lbf_b64_encode_update_batch");
-}
 
 struct EncodeCall {
   lbf_b64_enc_state* enc;
@@ -44,11 +37,6 @@ struct EncodeCall {
   uint32_t* new_lens;
   uint32_t* text_sizes;
 };
-
-// Below this many characters per run on average the text comes back as one
-// copy of the launch's area and is scattered on the host (b64_update_batch.cpp's
-// figure, as little measured here as there).
-constexpr uint64_t kDirectRunBytes = 64 << 10;
 
 // One launch: the cuts' state pairs, tables and bytes up, the kernels, states
 // and results back into the caller's arrays.
@@ -71,22 +59,17 @@ int encode_run_launch(lbf_ctx* ctx, hipStream_t st, const EncodeCall& c, const s
   }
   std::vector<B64EncPlace> places;
   const uint64_t text_area = b64_encode_places(spans, places);
-  // one block of tables, up and back: encoder states | SHA states | piece offsets | slot starts | new offsets |
-  // piece sizes | caps | new lengths | text lengths | expected | digests | final flags | verdicts
-  const uint64_t sha_at = 16 * m, off_at = sha_at + 96 * m, slot_at = off_at + 8 * m, noff_at = slot_at + 8 * m,
-                 size_at = noff_at + 8 * m, cap_at = size_at + 4 * m, nlen_at = cap_at + 4 * m,
-                 tsize_at = nlen_at + 4 * m, exp_at = tsize_at + 4 * m, dig_at = exp_at + 20 * m,
-                 fin_at = dig_at + 20 * m, ver_at = fin_at + m, tab_bytes = ver_at + m;
-  std::vector<uint8_t> tab(tab_bytes, 0), chars;
+  const EncodeTables at = encode_tables(m);  // one block of tables, up and back
+  std::vector<uint8_t> tab(at.bytes, 0);
   SyncOnExit sync{st};  // after the vectors the copies use: every exit waits for the stream before they go
-  lbf_b64_enc_state* h_enc = reinterpret_cast<lbf_b64_enc_state*>(tab.data());
-  lbf_sha1_state* h_sha = reinterpret_cast<lbf_sha1_state*>(tab.data() + sha_at);
-  uint64_t* h_off = reinterpret_cast<uint64_t*>(tab.data() + off_at);
-  uint64_t* h_slot = reinterpret_cast<uint64_t*>(tab.data() + slot_at);
-  uint32_t* h_size = reinterpret_cast<uint32_t*>(tab.data() + size_at);
-  uint32_t* h_cap = reinterpret_cast<uint32_t*>(tab.data() + cap_at);
-  const uint32_t* h_nlen = reinterpret_cast<const uint32_t*>(tab.data() + nlen_at);
-  const uint32_t* h_tsize = reinterpret_cast<const uint32_t*>(tab.data() + tsize_at);
+  lbf_b64_enc_state* h_enc = reinterpret_cast<lbf_b64_enc_state*>(tab.data() + at.enc);
+  lbf_sha1_state* h_sha = reinterpret_cast<lbf_sha1_state*>(tab.data() + at.sha);
+  uint64_t* h_off = reinterpret_cast<uint64_t*>(tab.data() + at.off);
+  uint64_t* h_slot = reinterpret_cast<uint64_t*>(tab.data() + at.slot);
+  uint32_t* h_size = reinterpret_cast<uint32_t*>(tab.data() + at.size);
+  uint32_t* h_cap = reinterpret_cast<uint32_t*>(tab.data() + at.cap);
+  const uint32_t* h_nlen = reinterpret_cast<const uint32_t*>(tab.data() + at.nlen);
+  const uint32_t* h_tsize = reinterpret_cast<const uint32_t*>(tab.data() + at.tsize);
   for (uint64_t k = 0; k < m; ++k) {
     const uint64_t i = cuts[k].piece, s = update_state_of(c.state_of, i);
     h_enc[k] = c.enc[s];
@@ -95,12 +78,13 @@ int encode_run_launch(lbf_ctx* ctx, hipStream_t st, const EncodeCall& c, const s
     h_slot[k] = places[k].slot;
     h_size[k] = cuts[k].size;
     h_cap[k] = c.text_caps[i];
-    if (c.expected) memcpy(tab.data() + exp_at + 20 * k, c.expected + 20 * i, 20);
-    tab[fin_at + k] = fin[k];
+    if (c.expected) memcpy(tab.data() + at.exp + 20 * k, c.expected + 20 * i, 20);
+    tab[at.fin + k] = fin[k];
   }
   // device layout: piece bytes | text | tables
-  const uint64_t data_b = up(data_area + 16, 256), text_b = up(text_area + 16, 256);
-  if (int rc = encode_scratch(ctx, data_b + text_b + up(tab_bytes, 256))) return rc;
+  const uint64_t data_b = round_up(data_area + 16, 256), text_b = round_up(text_area + 16, 256);
+  if (int rc = update_scratch(ctx, data_b + text_b + round_up(at.bytes, 256), "lbf_b64_encode_update_batch"))
+    return rc;
   uint8_t* d_data = ctx->upd_dev;
   uint8_t* d_text = d_data + data_b;
   uint8_t* d_tab = d_text + text_b;
@@ -108,12 +92,13 @@ int encode_run_launch(lbf_ctx* ctx, hipStream_t st, const EncodeCall& c, const s
     LBF_HIP_TRY(hipMemcpyAsync(d_data + r.dst, c.data + r.src, r.len, hipMemcpyHostToDevice, st));
   LBF_HIP_TRY(hipMemcpyAsync(d_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, st));
   if (int rc = lbf_b64_encode_update_launch(
-          reinterpret_cast<lbf_b64_enc_state*>(d_tab), reinterpret_cast<lbf_sha1_state*>(d_tab + sha_at), m, nullptr,
-          d_data, reinterpret_cast<const uint64_t*>(d_tab + off_at), reinterpret_cast<const uint32_t*>(d_tab + size_at),
-          d_tab + fin_at, m, reinterpret_cast<char*>(d_text), reinterpret_cast<const uint64_t*>(d_tab + slot_at),
-          reinterpret_cast<const uint32_t*>(d_tab + cap_at), reinterpret_cast<uint64_t*>(d_tab + noff_at),
-          reinterpret_cast<uint32_t*>(d_tab + nlen_at), reinterpret_cast<uint32_t*>(d_tab + tsize_at), d_tab + dig_at,
-          c.expected ? d_tab + exp_at : nullptr, c.expected ? d_tab + ver_at : nullptr, st))
+          reinterpret_cast<lbf_b64_enc_state*>(d_tab + at.enc), reinterpret_cast<lbf_sha1_state*>(d_tab + at.sha), m,
+          nullptr, d_data, reinterpret_cast<const uint64_t*>(d_tab + at.off),
+          reinterpret_cast<const uint32_t*>(d_tab + at.size), d_tab + at.fin, m, reinterpret_cast<char*>(d_text),
+          reinterpret_cast<const uint64_t*>(d_tab + at.slot), reinterpret_cast<const uint32_t*>(d_tab + at.cap),
+          reinterpret_cast<uint64_t*>(d_tab + at.noff), reinterpret_cast<uint32_t*>(d_tab + at.nlen),
+          reinterpret_cast<uint32_t*>(d_tab + at.tsize), d_tab + at.dig, c.expected ? d_tab + at.exp : nullptr,
+          c.expected ? d_tab + at.ver : nullptr, st))
     return rc;
   LBF_HIP_TRY(hipMemcpyAsync(tab.data(), d_tab, tab.size(), hipMemcpyDeviceToHost, st));
   LBF_HIP_TRY(hipStreamSynchronize(st));
@@ -126,19 +111,8 @@ int encode_run_launch(lbf_ctx* ctx, hipStream_t st, const EncodeCall& c, const s
     if (got[k] != places[k].room)
       return fail(LBF_ERR_HIP, "lbf_b64_encode_update_batch: a piece wrote other characters than planned (internal error)");
   }
-  b64_encode_copyback(dev_at, host_at, got, back_runs);
-  if (total && c.text) {
-    if (total / back_runs.size() >= kDirectRunBytes) {
-      for (const Run& r : back_runs)
-        LBF_HIP_TRY(hipMemcpyAsync(c.text + r.dst, d_text + r.src, r.len, hipMemcpyDeviceToHost, st));
-      LBF_HIP_TRY(hipStreamSynchronize(st));
-    } else {
-      chars.resize(text_area);
-      LBF_HIP_TRY(hipMemcpyAsync(chars.data(), d_text, text_area, hipMemcpyDeviceToHost, st));
-      LBF_HIP_TRY(hipStreamSynchronize(st));
-      for (const Run& r : back_runs) memcpy(c.text + r.dst, chars.data() + r.src, r.len);
-    }
-  }
+  copyback_runs(dev_at, host_at, got, back_runs);
+  if (int rc = copy_back(st, back_runs, total, text_area, d_text, c.text)) return rc;
   for (uint64_t k = 0; k < m; ++k) {
     const uint64_t i = cuts[k].piece, s = update_state_of(c.state_of, i);
     c.enc[s] = h_enc[k];
@@ -148,7 +122,7 @@ int encode_run_launch(lbf_ctx* ctx, hipStream_t st, const EncodeCall& c, const s
     if (c.new_lens) c.new_lens[i] = (first ? 0u : c.new_lens[i]) + got[k];
     if (!fin[k]) continue;  // only final pieces report
     if (c.text_sizes) c.text_sizes[i] = h_tsize[k];
-    if (c.verdicts) c.verdicts[i] = tab[ver_at + k];
+    if (c.verdicts) c.verdicts[i] = tab[at.ver + k];
   }
   return LBF_OK;
 }
@@ -162,31 +136,16 @@ extern "C" int lbf_b64_encode_update_batch(lbf_ctx* ctx, lbf_b64_enc_state* enc_
                                            uint8_t* verdicts, char* text, uint64_t text_len,
                                            const uint64_t* text_offsets, const uint32_t* text_caps,
                                            uint64_t* new_offsets, uint32_t* new_lens, uint32_t* text_sizes) {
-  const std::string who = "lbf_b64_encode_update_batch";
-  if (!ctx) return fail(LBF_ERR_INVALID, "null context");
-  if (n == 0) return LBF_OK;
-  if (!enc_states || !sha_states || !data || !offsets || !sizes || !text_offsets || !text_caps)
-    return fail(LBF_ERR_INVALID, who + ": null argument");
-  if (!text && text_len) return fail(LBF_ERR_INVALID, who + ": text is null but text_len is not 0");
-  if (n > 0x7FFFFFFFull) return fail(LBF_ERR_INVALID, who + ": n too large");
-  if ((verdicts != nullptr) != (expected != nullptr))
-    return fail(LBF_ERR_INVALID, who + ": expected and verdicts go together");
-  return guarded([&]() -> int {
-    std::string why;
-    const uint64_t bad = b64_encode_check(enc_states, sha_states, n_states, state_of, data_len, offsets, sizes, n,
-                                          text ? text_len : 0, text_offsets, text_caps, why);
-    if (bad != kNoPiece) return fail(LBF_ERR_INVALID, who + ": piece " + std::to_string(bad) + " " + why);
-    const std::vector<std::vector<UpdateCut>> launches = update_launches(offsets, sizes, n, ctx->update_bytes);
-    const EncodeCall call{enc_states, sha_states, state_of,     data,         offsets,   final_flags, expected,
-                          verdicts,   reinterpret_cast<uint8_t*>(text), text_offsets, text_caps, new_offsets,
-                          new_lens,   text_sizes};
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    KeepCurrentDevice keep;
-    Worker& w = ctx->workers[0];
-    LBF_HIP_TRY(hipSetDevice(w.device));
-    hipStream_t st = w.dev[0].stream;
-    for (const std::vector<UpdateCut>& cuts : launches)
-      if (int rc = encode_run_launch(ctx, st, call, cuts)) return rc;
-    return (int)LBF_OK;
-  });
+  const EncodeCall call{enc_states, sha_states, state_of,     data,         offsets,   final_flags, expected,
+                        verdicts,   reinterpret_cast<uint8_t*>(text), text_offsets, text_caps, new_offsets,
+                        new_lens,   text_sizes};
+  return update_call(
+      ctx, "lbf_b64_encode_update_batch", n,
+      !enc_states || !sha_states || !data || !offsets || !sizes || !text_offsets || !text_caps,
+      !text && text_len ? "text is null but text_len is not 0" : nullptr, expected, verdicts, offsets, sizes,
+      [&](std::string& why) {
+        return b64_encode_check(enc_states, sha_states, n_states, state_of, data_len, offsets, sizes, n,
+                                text ? text_len : 0, text_offsets, text_caps, why);
+      },
+      [&](hipStream_t st, const std::vector<UpdateCut>& cuts) { return encode_run_launch(ctx, st, call, cuts); });
 }

@@ -1,9 +1,10 @@
 // b64_encode_plan.hpp -- the arithmetic of lbf_b64_encode_update_batch: which
 // calls are refused, which characters of its chunk's text a piece writes, where
 // a launch's characters lie on the device (at their text position mod 16, so
-// the kernel's 16-byte stores apply), and how they are copied back.  Pieces are
-// cut into launches by update_plan.hpp's update_launches (an encoder state may
-// be stopped at any byte, so its cuts at multiples of 64 do).  No HIP, no
+// the kernel's 16-byte stores apply), and where its tables lie.  Pieces are cut
+// into launches by update_plan.hpp's update_launches (an encoder state may be
+// stopped at any byte, so its cuts at multiples of 64 do), and the characters
+// come back by its copyback_runs.  No HIP, no
 // threads, no environment, no I/O: every rule here runs in a CPU test
 // (tests/c/b64_encode_plan_tests.cpp).  b64_encode_batch.cpp drives the stream
 // with it.
@@ -13,6 +14,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "b64_encode_update.hpp"
@@ -72,35 +74,11 @@ inline uint64_t b64_encode_check(const lbf_b64_enc_state* enc, const lbf_sha1_st
       return i;
     }
   }
-  std::vector<uint64_t> idx(n);
-  for (uint64_t i = 0; i < n; ++i) idx[i] = i;
-  if (state_of) {  // two pieces of one state: the order they would be encoded in is undefined
-    std::sort(idx.begin(), idx.end(),
-              [&](uint64_t a, uint64_t b) { return state_of[a] != state_of[b] ? state_of[a] < state_of[b] : a < b; });
-    uint64_t bad = kNoPiece;
-    for (uint64_t k = 1; k < n; ++k)
-      if (state_of[idx[k]] == state_of[idx[k - 1]]) bad = std::min(bad, idx[k]);
-    if (bad != kNoPiece) {
-      why = "is the second piece of state " + std::to_string(state_of[bad]) + " in one call";
-      return bad;
-    }
-  }
-  // slots of different states may touch but not overlap (empty slots hold nothing)
-  std::sort(idx.begin(), idx.end(), [&](uint64_t a, uint64_t b) {
-    return text_offsets[a] != text_offsets[b] ? text_offsets[a] < text_offsets[b] : a < b;
-  });
-  uint64_t bad = kNoPiece, end = 0;
-  for (uint64_t k = 0; k < n; ++k) {
-    const uint64_t i = idx[k];
-    if (text_caps[i] == 0) continue;
-    if (text_offsets[i] < end) bad = std::min(bad, i);
-    end = std::max(end, text_offsets[i] + text_caps[i]);
-  }
-  if (bad != kNoPiece) {
-    why = "has a slot that overlaps another state's";
-    return bad;
-  }
-  return kNoPiece;
+  const uint64_t second = second_piece_of_a_state(state_of, n, why);
+  if (second != kNoPiece) return second;
+  std::vector<uint64_t> all(n);
+  for (uint64_t i = 0; i < n; ++i) all[i] = i;
+  return slot_overlap(std::move(all), text_offsets, text_caps, why);
 }
 
 // The characters of its chunk's text that a cut writes: positions [lo, hi),
@@ -140,12 +118,30 @@ inline uint64_t b64_encode_places(const std::vector<B64EncSpan>& spans, std::vec
   return cursor;
 }
 
-// Copy-back: cut k put size[k] characters at device position dev[k], which
-// belong at host position host[k]; ranges that touch on both sides travel as
-// one run (b64_update_plan.hpp's rule).
-inline void b64_encode_copyback(const std::vector<uint64_t>& dev, const std::vector<uint64_t>& host,
-                                const std::vector<uint32_t>& size, std::vector<Run>& runs) {
-  b64_update_copyback(dev, host, size, runs);
+// Where the tables of one encode launch of m cuts lie in the one block that
+// goes up and comes back.
+struct EncodeTables {
+  uint64_t enc, sha, off, slot, noff, size, cap, nlen, tsize, exp, dig, fin, ver, bytes;
+};
+
+inline EncodeTables encode_tables(uint64_t m) {
+  TableLayout l;
+  EncodeTables t;
+  t.enc = l.take(16 * m);
+  t.sha = l.take(96 * m);
+  t.off = l.take(8 * m);    // piece offsets
+  t.slot = l.take(8 * m);   // slot starts
+  t.noff = l.take(8 * m);   // new offsets
+  t.size = l.take(4 * m);   // piece sizes
+  t.cap = l.take(4 * m);
+  t.nlen = l.take(4 * m);   // new lengths
+  t.tsize = l.take(4 * m);  // text lengths
+  t.exp = l.take(20 * m);
+  t.dig = l.take(20 * m);
+  t.fin = l.take(m);
+  t.ver = l.take(m);
+  t.bytes = l.bytes;
+  return t;
 }
 
 }  // namespace lbf

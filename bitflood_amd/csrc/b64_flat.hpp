@@ -1,4 +1,4 @@
-// b64_flat.hpp -- what wire_batch.cpp, b64_update.hip and b64_update_batch.cpp
+// b64_flat.hpp -- what wire_batch.cpp, b64_update.hip and update_batch.cpp
 // need of the flat path of the base64 decode (b64_flat.hip): unbroken RFC 4648
 // text, as bitflood's Java and Perl peers frame a chunk -- character i is
 // sextet i, no line separators.  Two launchers (the one-shot pass of

@@ -1,4 +1,4 @@
-// b64_update_lines.hpp -- what b64_update.hip and b64_update_batch.cpp need of
+// b64_update_lines.hpp -- what b64_update.hip and update_batch.cpp need of
 // the line path of the piecewise decode (b64_update_lines.hip): its launcher,
 // the process-wide switch, and the launch that also reports, per piece, the
 // characters the line path took.  Not part of the ABI.
@@ -48,5 +48,17 @@ int b64_update_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha
                               uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                               uint64_t* d_piece_offsets, uint32_t* d_piece_sizes, uint32_t* d_line_chars,
                               uint32_t* d_flat_chars, void* stream);
+
+// lbf_b64_update_seq_launch with two more device arrays (each null, or n
+// entries): the characters of each piece that the line stage and the flat
+// stage took, as b64_update_launch_counted reports them.
+int b64_update_seq_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
+                                  const uint32_t* d_chain_state, const uint32_t* d_chain_first, uint64_t n_chains,
+                                  const char* d_text, const uint64_t* d_text_offsets, const uint32_t* d_text_lens,
+                                  const uint8_t* d_final, uint64_t n, uint8_t* d_out, const uint64_t* d_out_offsets,
+                                  const uint32_t* d_caps, uint32_t* d_out_sizes, uint8_t* d_digests,
+                                  const uint8_t* d_expected, uint8_t* d_verdicts, uint64_t* d_piece_offsets,
+                                  uint32_t* d_piece_sizes, uint32_t* d_line_chars, uint32_t* d_flat_chars,
+                                  void* stream);
 
 }  // namespace lbf

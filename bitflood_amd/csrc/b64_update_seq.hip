@@ -29,7 +29,6 @@
 #include "b64_flat.hpp"
 #include "b64_update_fused.hpp"
 #include "b64_update_lines.hpp"
-#include "b64_update_seq.hpp"
 #include "lbf_internal.hpp"
 
 // The stage functions' lane number, for this translation unit only: the
@@ -210,7 +209,6 @@ __global__ void __launch_bounds__(256) b64_length_seq_kernel(B64SeqParams p) {
 
 }  // namespace lbf
 
-using lbf::check_fits;
 using lbf::fail;
 
 extern "C" int lbf_b64_update_seq_launch(lbf_b64_state* d_b64_states, lbf_sha1_state* d_sha_states, uint64_t n_states,
@@ -250,30 +248,27 @@ int lbf::b64_update_seq_launch_counted(lbf_b64_state* d_b64_states, lbf_sha1_sta
     return fail(LBF_ERR_INVALID, who + ": digest/expected arrays must be 4-byte aligned");
   if ((reinterpret_cast<uintptr_t>(d_b64_states) & 15u) || (reinterpret_cast<uintptr_t>(d_sha_states) & 15u))
     return fail(LBF_ERR_INVALID, who + ": the state arrays must be 16-byte aligned");
-  if ((reinterpret_cast<uintptr_t>(d_text_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_out_offsets) & 7u) ||
-      (reinterpret_cast<uintptr_t>(d_piece_offsets) & 7u) || (reinterpret_cast<uintptr_t>(d_text_lens) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_caps) & 3u) || (reinterpret_cast<uintptr_t>(d_out_sizes) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_piece_sizes) & 3u) || (reinterpret_cast<uintptr_t>(d_chain_state) & 3u) ||
-      (reinterpret_cast<uintptr_t>(d_chain_first) & 3u))
-    return fail(LBF_ERR_INVALID, who + ": a table is not aligned to its element size");
+  const std::initializer_list<lbf::DevTable> tables = {
+      {d_b64_states, 16, n_states, "b64_states", false},
+      {d_sha_states, 96, n_states, "sha_states", false},
+      {d_chain_state, 4, n_chains, "chain_state", true},
+      {d_chain_first, 4, n_chains + 1, "chain_first", true},
+      {d_text_offsets, 8, n, "text_offsets", true},
+      {d_text_lens, 4, n, "text_lens", true},
+      {d_final, 1, n, "final", false},
+      {d_out_offsets, 8, n, "out_offsets", true},
+      {d_caps, 4, n, "caps", true},
+      {d_out_sizes, 4, n, "out_sizes", true},
+      {d_digests, 20, n, "digests", false},
+      {d_expected, 20, n, "expected", false},
+      {d_verdicts, 1, n, "verdicts", false},
+      {d_piece_offsets, 8, n, "piece_offsets", true},
+      {d_piece_sizes, 4, n, "piece_sizes", true},
+      {d_line_chars, 4, n, "line_chars", false},
+      {d_flat_chars, 4, n, "flat_chars", false}};
+  if (int rc = lbf::tables_aligned(who, tables)) return rc;
   if (n_states > UINT64_MAX / 96) return fail(LBF_ERR_INVALID, who + ": n_states too large");
-  if (int rc = check_fits(d_b64_states, 16 * n_states, "lbf_b64_update_seq_launch: b64_states")) return rc;
-  if (int rc = check_fits(d_sha_states, 96 * n_states, "lbf_b64_update_seq_launch: sha_states")) return rc;
-  if (int rc = check_fits(d_chain_state, 4 * n_chains, "lbf_b64_update_seq_launch: chain_state")) return rc;
-  if (int rc = check_fits(d_chain_first, 4 * (n_chains + 1), "lbf_b64_update_seq_launch: chain_first")) return rc;
-  if (int rc = check_fits(d_text_offsets, 8 * n, "lbf_b64_update_seq_launch: text_offsets")) return rc;
-  if (int rc = check_fits(d_text_lens, 4 * n, "lbf_b64_update_seq_launch: text_lens")) return rc;
-  if (int rc = check_fits(d_final, n, "lbf_b64_update_seq_launch: final")) return rc;
-  if (int rc = check_fits(d_out_offsets, 8 * n, "lbf_b64_update_seq_launch: out_offsets")) return rc;
-  if (int rc = check_fits(d_caps, 4 * n, "lbf_b64_update_seq_launch: caps")) return rc;
-  if (int rc = check_fits(d_out_sizes, 4 * n, "lbf_b64_update_seq_launch: out_sizes")) return rc;
-  if (int rc = check_fits(d_digests, 20 * n, "lbf_b64_update_seq_launch: digests")) return rc;
-  if (int rc = check_fits(d_expected, 20 * n, "lbf_b64_update_seq_launch: expected")) return rc;
-  if (int rc = check_fits(d_verdicts, n, "lbf_b64_update_seq_launch: verdicts")) return rc;
-  if (int rc = check_fits(d_piece_offsets, 8 * n, "lbf_b64_update_seq_launch: piece_offsets")) return rc;
-  if (int rc = check_fits(d_piece_sizes, 4 * n, "lbf_b64_update_seq_launch: piece_sizes")) return rc;
-  if (int rc = check_fits(d_line_chars, 4 * n, "lbf_b64_update_seq_launch: line_chars")) return rc;
-  if (int rc = check_fits(d_flat_chars, 4 * n, "lbf_b64_update_seq_launch: flat_chars")) return rc;
+  if (int rc = lbf::tables_fit(who, tables)) return rc;
   lbf::B64SeqParams p{};
   p.b64_states = reinterpret_cast<uint8_t*>(d_b64_states);
   p.n_states = n_states;

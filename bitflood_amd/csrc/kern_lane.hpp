@@ -13,43 +13,6 @@
 namespace lbf {
 namespace {
 
-__device__ __forceinline__ void load_block(uint4 (&q)[4], const uint4* src) {
-  q[0] = src[0];
-  q[1] = src[1];
-  q[2] = src[2];
-  q[3] = src[3];
-}
-
-// Full 64-byte blocks of a 16-byte aligned chunk, two blocks in flight ahead of
-// the compression that consumes them.
-__device__ __forceinline__ void hash_blocks_aligned(Digest& s, const uint8_t* src, uint32_t nblk) {
-  if (nblk == 0) return;
-  const uint4* q = reinterpret_cast<const uint4*>(src);
-  const uint32_t last = nblk - 1;
-  uint4 A[4], B[4];
-  load_block(A, q);
-  load_block(B, q + 4 * (last < 1u ? last : 1u));
-  for (uint32_t b = 0; b < nblk; ++b) {
-    uint4 C[4] = {A[0], A[1], A[2], A[3]};
-    A[0] = B[0]; A[1] = B[1]; A[2] = B[2]; A[3] = B[3];
-    const uint32_t nb = b + 2 < last ? b + 2 : last;  // clamp: re-read the last block
-    load_block(B, q + 4 * nb);
-    uint32_t w[16];
-    block_from_vec(w, C[0], C[1], C[2], C[3]);
-    compress(s, w);
-  }
-}
-
-__device__ __forceinline__ void hash_blocks_unaligned(Digest& s, const uint8_t* src, uint32_t nblk) {
-  for (uint32_t b = 0; b < nblk; ++b) {
-    uint32_t w[16];
-    load_words_any(w, src + 64ull * b, 64);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = bswap(w[k]);
-    compress(s, w);
-  }
-}
-
 template <bool kUniform>
 __global__ void __launch_bounds__(256) sha1_lane_kernel(ChunkParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

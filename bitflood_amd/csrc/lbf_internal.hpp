@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
 #include <string>
 
 #include "lbf_hash.h"
@@ -38,6 +39,32 @@ struct ChunkParams {
 // A device array the caller passed must fit in the allocation it points into
 // (sha1_kernels.hip); LBF_OK for null, empty, or memory HIP cannot place.
 int check_fits(const void* p, uint64_t bytes, const char* what);
+
+// One device array of a launch: `count` elements of `elem` bytes, by the name
+// the refusals use; `aligned` when the launch needs it aligned to its element.
+struct DevTable {
+  const void* p;
+  uint64_t elem, count;
+  const char* name;
+  bool aligned;
+};
+
+// The device launches' validator, in two passes that a launch may put refusals
+// of its own between: one refusal for the whole list when an array that needs
+// it is not aligned to its element size, then check_fits per array in list
+// order, named "<who>: <name>".
+inline int tables_aligned(const std::string& who, std::initializer_list<DevTable> tables) {
+  for (const DevTable& t : tables)
+    if (t.aligned && reinterpret_cast<uintptr_t>(t.p) % t.elem)
+      return fail(LBF_ERR_INVALID, who + ": a table is not aligned to its element size");
+  return LBF_OK;
+}
+
+inline int tables_fit(const std::string& who, std::initializer_list<DevTable> tables) {
+  for (const DevTable& t : tables)
+    if (int rc = check_fits(t.p, t.elem * t.count, (who + ": " + t.name).c_str())) return rc;
+  return LBF_OK;
+}
 
 int pick_variant(uint64_t n);
 int launch_chunks(const ChunkParams& p, hipStream_t stream);

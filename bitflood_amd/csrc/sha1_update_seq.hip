@@ -18,14 +18,12 @@
 // byte-wise as in sha1_update.hip (a register array indexed by `buffered` would
 // live in scratch); the 32 header bytes are read once and written once.
 //
-// A translation unit of its own: the shipped kernels' ISA stays as recorded
-// (tests/test_isa.py), so the block loops and finish64 of sha1_update.hip are
-// restated here, as that file restates kern_lane.hpp's.  DESIGN.md §4.9.
+// The block loops are sha1_device.hpp's, the record's layout, finish64 and a
+// final piece's outputs sha1_resume.hpp's, as in sha1_update.hip.  DESIGN.md §4.9.
 #include <hip/hip_runtime.h>
-#include <stddef.h>
 
 #include "lbf_internal.hpp"
-#include "sha1_device.hpp"
+#include "sha1_resume.hpp"
 
 namespace lbf {
 
@@ -46,80 +44,6 @@ struct UpdateSeqParams {
   const uint8_t* expected;      // n*20 or null
   uint8_t* verdicts;            // n or null; written for final pieces only
 };
-
-constexpr uint32_t kStateBytes = 96, kBlockAt = 32;
-static_assert(sizeof(lbf_sha1_state) == kStateBytes, "lbf_sha1_state is 96 bytes");
-static_assert(offsetof(lbf_sha1_state, buffered) == 20 && offsetof(lbf_sha1_state, total) == 24 &&
-                  offsetof(lbf_sha1_state, block) == kBlockAt,
-              "lbf_sha1_state layout");
-
-// Full 64-byte blocks of a 16-byte aligned range, two blocks in flight ahead of
-// the compression that consumes them (sha1_update.hip, kern_lane.hpp).
-__device__ __forceinline__ void load_block(uint4 (&q)[4], const uint4* src) {
-  q[0] = src[0];
-  q[1] = src[1];
-  q[2] = src[2];
-  q[3] = src[3];
-}
-
-__device__ __forceinline__ void update_blocks_aligned(Digest& s, const uint8_t* src, uint32_t nblk) {
-  if (nblk == 0) return;
-  const uint4* q = reinterpret_cast<const uint4*>(src);
-  const uint32_t last = nblk - 1;
-  uint4 A[4], B[4];
-  load_block(A, q);
-  load_block(B, q + 4 * (last < 1u ? last : 1u));
-  for (uint32_t b = 0; b < nblk; ++b) {
-    uint4 C[4] = {A[0], A[1], A[2], A[3]};
-    A[0] = B[0]; A[1] = B[1]; A[2] = B[2]; A[3] = B[3];
-    const uint32_t nb = b + 2 < last ? b + 2 : last;  // clamp: re-read the last block
-    load_block(B, q + 4 * nb);
-    uint32_t w[16];
-    block_from_vec(w, C[0], C[1], C[2], C[3]);
-    compress(s, w);
-  }
-}
-
-__device__ __forceinline__ void update_blocks_unaligned(Digest& s, const uint8_t* src, uint32_t nblk) {
-  for (uint32_t b = 0; b < nblk; ++b) {
-    uint32_t w[16];
-    load_words_any(w, src + 64ull * b, 64);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = bswap(w[k]);
-    compress(s, w);
-  }
-}
-
-// The record's block as 16 big-endian words (four 16-byte loads).
-__device__ __forceinline__ void record_block(uint32_t (&w)[16], const uint8_t* blk) {
-  const uint4* q = reinterpret_cast<const uint4*>(blk);
-  const uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3];
-  block_from_vec(w, q0, q1, q2, q3);
-}
-
-// Final one or two compressions from the r (< 64) bytes held in `w`: 0x80 pad,
-// zeros, and the bit length of `total` bytes in words 14-15 (sha1_update.hip).
-__device__ __forceinline__ void finish64(Digest& s, uint32_t (&w)[16], uint32_t r, uint64_t total) {
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int rem = (int)r - 4 * k;  // message bytes left in this word
-    uint32_t v = w[k];
-    if (rem <= 0) v = 0;
-    if (rem >= 0 && rem < 4) {
-      const uint32_t sh = 8u * (uint32_t)rem;
-      v = (v & ~(0xFFFFFFFFu >> sh)) | (0x80000000u >> sh);  // keep `rem` bytes, then 0x80
-    }
-    w[k] = v;
-  }
-  if (r >= 56) {
-    compress(s, w);
-#pragma unroll
-    for (int k = 0; k < 16; ++k) w[k] = 0;
-  }
-  w[14] = (uint32_t)(total >> 29);
-  w[15] = (uint32_t)(total << 3);
-  compress(s, w);
-}
 
 __global__ void __launch_bounds__(256) sha1_update_seq_kernel(UpdateSeqParams p) {
   const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -169,9 +93,9 @@ __global__ void __launch_bounds__(256) sha1_update_seq_kernel(UpdateSeqParams p)
     const uint32_t nblk = size >> 6;
     if (nblk) {  // the loop is chosen per piece, by where its full blocks start
       if ((reinterpret_cast<uintptr_t>(src) & 15u) == 0) {
-        update_blocks_aligned(s, src, nblk);
+        hash_blocks_aligned(s, src, nblk);
       } else {
-        update_blocks_unaligned(s, src, nblk);
+        hash_blocks_unaligned(s, src, nblk);
       }
       src += 64ull * nblk;
     }
@@ -186,18 +110,7 @@ __global__ void __launch_bounds__(256) sha1_update_seq_kernel(UpdateSeqParams p)
     uint32_t be[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) be[k] = bswap(s.h[k]);  // digest bytes in big-endian order
-    if (p.digests) {
-      uint32_t* o = reinterpret_cast<uint32_t*>(p.digests + 20ull * i);
-#pragma unroll
-      for (int k = 0; k < 5; ++k) o[k] = be[k];
-    }
-    if (p.verdicts) {
-      const uint32_t* e = reinterpret_cast<const uint32_t*>(p.expected + 20ull * i);
-      uint32_t diff = 0;
-#pragma unroll
-      for (int k = 0; k < 5; ++k) diff |= be[k] ^ e[k];
-      p.verdicts[i] = diff == 0 ? 1 : 0;
-    }
+    write_final(p, i, be);
     // Final() restarts the object (iterhash.h:120): the registers and the block
     // are as lbf_sha1_state_init leaves them, and the pieces that follow begin
     // a new chunk
@@ -216,7 +129,6 @@ __global__ void __launch_bounds__(256) sha1_update_seq_kernel(UpdateSeqParams p)
 
 }  // namespace lbf
 
-using lbf::check_fits;
 using lbf::fail;
 
 extern "C" int lbf_sha1_update_seq_launch(lbf_sha1_state* d_states, uint64_t n_states, const uint32_t* d_chain_state,
@@ -241,15 +153,16 @@ extern "C" int lbf_sha1_update_seq_launch(lbf_sha1_state* d_states, uint64_t n_s
   if ((reinterpret_cast<uintptr_t>(d_chain_state) & 3u) || (reinterpret_cast<uintptr_t>(d_chain_first) & 3u))
     return fail(LBF_ERR_INVALID, who + ": the chain table must be 4-byte aligned");
   if (n_states > UINT64_MAX / 96) return fail(LBF_ERR_INVALID, who + ": n_states too large");
-  if (int rc = check_fits(d_states, 96 * n_states, "lbf_sha1_update_seq_launch: states")) return rc;
-  if (int rc = check_fits(d_chain_state, 4 * n_chains, "lbf_sha1_update_seq_launch: chain_state")) return rc;
-  if (int rc = check_fits(d_chain_first, 4 * (n_chains + 1), "lbf_sha1_update_seq_launch: chain_first")) return rc;
-  if (int rc = check_fits(d_offsets, 8 * n, "lbf_sha1_update_seq_launch: offsets")) return rc;
-  if (int rc = check_fits(d_sizes, 4 * n, "lbf_sha1_update_seq_launch: sizes")) return rc;
-  if (int rc = check_fits(d_final, n, "lbf_sha1_update_seq_launch: final")) return rc;
-  if (int rc = check_fits(d_digests, 20 * n, "lbf_sha1_update_seq_launch: digests")) return rc;
-  if (int rc = check_fits(d_expected, 20 * n, "lbf_sha1_update_seq_launch: expected")) return rc;
-  if (int rc = check_fits(d_verdicts, n, "lbf_sha1_update_seq_launch: verdicts")) return rc;
+  if (int rc = lbf::tables_fit(who, {{d_states, 96, n_states, "states", false},
+                                      {d_chain_state, 4, n_chains, "chain_state", false},
+                                      {d_chain_first, 4, n_chains + 1, "chain_first", false},
+                                      {d_offsets, 8, n, "offsets", false},
+                                      {d_sizes, 4, n, "sizes", false},
+                                      {d_final, 1, n, "final", false},
+                                      {d_digests, 20, n, "digests", false},
+                                      {d_expected, 20, n, "expected", false},
+                                      {d_verdicts, 1, n, "verdicts", false}}))
+    return rc;
   lbf::UpdateSeqParams p{};
   p.states = reinterpret_cast<uint8_t*>(d_states);
   p.n_states = n_states;

@@ -57,6 +57,9 @@ struct Run {
   uint32_t file = 0;
 };
 
+// x rounded up to a multiple of a: the sizes of the areas runs are copied into.
+inline uint64_t round_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
+
 // Descriptors closer than this to the end of the current run join it: the gap
 // is copied along (cheaper than another copy); the 16-byte padding between
 // ReadVerifiedChunks' arena slots is the common case.

@@ -202,11 +202,30 @@ static void test_places_and_copyback() {
   std::vector<uint64_t> dev = {0, 68, 200, 232, 300}, host = {1000, 1068, 5000, 5033, 7000};
   std::vector<uint32_t> size = {68, 5, 32, 10, 0};
   std::vector<Run> runs;
-  b64_encode_copyback(dev, host, size, runs);
+  copyback_runs(dev, host, size, runs);
   CHECK(runs.size() == 3);
   CHECK(runs[0].src == 0 && runs[0].dst == 1000 && runs[0].len == 73);
   CHECK(runs[1].src == 200 && runs[1].dst == 5000 && runs[1].len == 32);  // touches on the device only
   CHECK(runs[2].src == 232 && runs[2].dst == 5033 && runs[2].len == 10);
+}
+
+// Where an encode launch's tables lie: the numbers of the hand-written offset
+// chain the layout replaced.  Encoder states (16 m) | SHA states (96 m) | piece
+// offsets, slot starts, new offsets (8 m each) | piece sizes, caps, new
+// lengths, text lengths (4 m each) | expected, digests (20 m each) | final
+// flags, verdicts (m each).
+static void test_table_offsets() {
+  struct Want { uint64_t m, at[13]; };  // sha ... ver, bytes
+  const Want want[3] = {{1, {16, 112, 120, 128, 136, 140, 144, 148, 152, 172, 192, 193, 194}},
+                        {2, {32, 224, 240, 256, 272, 280, 288, 296, 304, 344, 384, 386, 388}},
+                        {7, {112, 784, 840, 896, 952, 980, 1008, 1036, 1064, 1204, 1344, 1351, 1358}}};
+  for (const Want& w : want) {
+    const EncodeTables t = encode_tables(w.m);
+    const uint64_t got[13] = {t.sha,  t.off,   t.slot, t.noff, t.size, t.cap, t.nlen,
+                              t.tsize, t.exp,  t.dig,  t.fin,  t.ver,  t.bytes};
+    CHECK(t.enc == 0);
+    for (int k = 0; k < 13; ++k) CHECK(got[k] == w.at[k]);
+  }
 }
 
 int main() {
@@ -215,6 +234,7 @@ int main() {
   test_oversized_piece_is_cut();
   test_spans();
   test_places_and_copyback();
+  test_table_offsets();
   if (g_fail) {
     std::printf("b64_encode_plan_tests: %d FAILED\n", g_fail);
     return 1;

@@ -6,6 +6,8 @@
 // -fsanitize=address,undefined and runs both.
 #include "b64_update_plan.hpp"
 
+#include "check_cases.hpp"
+
 #include <cstdio>
 #include <cstring>
 
@@ -161,7 +163,7 @@ static void test_places() {
   const std::vector<uint32_t> len = {100, 8, 4096, 40, 40, 5, 0};
   const std::vector<uint32_t> cap = {300, 300, 1u << 20, 300, 300, 64, 0};
   std::vector<B64Place> pl;
-  const uint64_t area = b64_update_places(decoded, ncarry, len, cap, pl);
+  const uint64_t area = b64_update_places(decoded, ncarry, std::vector<uint64_t>(len.begin(), len.end()), cap, pl);
   uint64_t end = 0;
   for (size_t k = 0; k < pl.size(); ++k) {
     const uint64_t at = std::min<uint64_t>(decoded[k], cap[k]);
@@ -183,14 +185,14 @@ static void test_places() {
 static void test_copyback() {
   std::vector<Run> runs;
   // touching on both sides joins; touching on one side only does not; empty pieces vanish
-  b64_update_copyback({0, 10, 30, 64, 100}, {500, 510, 520, 900, 904}, {10, 10, 0, 4, 7}, runs);
+  copyback_runs({0, 10, 30, 64, 100}, {500, 510, 520, 900, 904}, {10, 10, 0, 4, 7}, runs);
   CHECK(runs.size() == 3);
   CHECK(runs[0].src == 0 && runs[0].dst == 500 && runs[0].len == 20);
   CHECK(runs[1].src == 64 && runs[1].dst == 900 && runs[1].len == 4);
   CHECK(runs[2].src == 100 && runs[2].dst == 904 && runs[2].len == 7);
-  b64_update_copyback({0, 10}, {500, 511}, {10, 10}, runs);
+  copyback_runs({0, 10}, {500, 511}, {10, 10}, runs);
   CHECK(runs.size() == 2);
-  b64_update_copyback({}, {}, {}, runs);
+  copyback_runs({}, {}, {}, runs);
   CHECK(runs.empty());
 }
 
@@ -267,7 +269,7 @@ static void test_past_4gib() {
   const std::vector<uint32_t> ncarry = {0, 1, 2, 3};
   const std::vector<uint32_t> len(tlen, tlen + 4), cap(caps, caps + 4);
   std::vector<B64Place> pl;
-  const uint64_t area = b64_update_places(decoded, ncarry, len, cap, pl);
+  const uint64_t area = b64_update_places(decoded, ncarry, std::vector<uint64_t>(len.begin(), len.end()), cap, pl);
   CHECK(area < 1024);
   for (size_t k = 0; k < 4; ++k) {
     const uint64_t at = std::min<uint64_t>(decoded[k], cap[k]);
@@ -276,15 +278,67 @@ static void test_past_4gib() {
   CHECK(pl[1].room == 0 && pl[2].room == 0 && pl[0].room == 50 && pl[3].room == 15);
 
   // copy-back: host positions are 64-bit; runs join across the line when both sides touch
-  b64_update_copyback({0, 64, 140, 320}, {G - 70, G - 6, G + 64, 3 * G + 5}, {64, 70, 75, 24}, runs);
+  copyback_runs({0, 64, 140, 320}, {G - 70, G - 6, G + 64, 3 * G + 5}, {64, 70, 75, 24}, runs);
   CHECK(runs.size() == 3);
   if (runs.size() == 3) {
     CHECK(runs[0].src == 0 && runs[0].dst == G - 70 && runs[0].len == 134);  // across the line in one run
     CHECK(runs[1].src == 140 && runs[1].dst == G + 64 && runs[1].len == 75);  // host side touches, device side does not
     CHECK(runs[2].src == 320 && runs[2].dst == 3 * G + 5 && runs[2].len == 24);
   }
-  b64_update_copyback({0, 64}, {G - 64, 2 * G}, {64, 10}, runs);  // host positions equal mod 2^32 do not touch
+  copyback_runs({0, 64}, {G - 64, 2 * G}, {64, 10}, runs);  // host positions equal mod 2^32 do not touch
   CHECK(runs.size() == 2 && runs[1].dst == 2 * G);
+}
+
+// The one-piece and the seq checker over seeded calls (check_cases.hpp): each
+// answers what tests/golden/plan_checks.txt records of the checkers before the
+// planners were merged, and where no state repeats the two agree to the word.
+static void test_checkers_agree() {
+  using namespace plan_cases;
+  const std::vector<Recorded> want = read_fixture(fixture_path(__FILE__));
+  CHECK(want.size() == kCases);
+  if (want.size() != kCases) return;
+  uint64_t refused = 0;
+  for (uint64_t k = 0; k < kCases; ++k) {
+    const Case c = make_case(k);
+    CHECK(checksum(c) == want[k].sum);
+    Answer one, seq;
+    one.piece = b64_update_check(c.b64.data(), c.sha.data(), c.n_states, c.so(), c.text_len, c.text_offsets.data(),
+                                 c.text_lens.data(), c.n, c.caps.data(), c.out_len, c.out_offsets.data(), one.why);
+    seq.piece = b64_update_seq_check(c.b64.data(), c.sha.data(), c.n_states, c.so(), c.text_len,
+                                     c.text_offsets.data(), c.text_lens.data(), nullptr, c.n, c.caps.data(), c.out_len,
+                                     c.out_offsets.data(), seq.why);
+    CHECK(one == want[k].text_one);
+    CHECK(seq == want[k].text_seq);
+    if (!c.repeats) CHECK(one == seq);
+    refused += one.piece != kNoPiece;
+  }
+  CHECK(refused > kCases / 4);
+}
+
+// Where a text launch's tables lie: the numbers of the hand-written offset
+// chains the layout replaced.  b64 states (16 nc) | SHA states (96 nc) | text
+// offsets, slot starts, piece offsets (8 m each) | seq only: chain_first
+// (4 (nc + 1)) | text lengths, chunk sizes, piece sizes, decoded lengths, line
+// and flat characters (4 m each) | expected, digests (20 m each) | final flags,
+// verdicts (m each).
+static void test_table_offsets() {
+  struct Want { uint64_t m, nc; bool seq; uint64_t at[16]; };  // sha ... ver, bytes, in the order above
+  const Want want[8] = {
+      {1, 1, false, {16, 112, 120, 128, 136, 136, 140, 144, 148, 152, 156, 160, 180, 200, 201, 202}},
+      {2, 2, false, {32, 224, 240, 256, 272, 272, 280, 288, 296, 304, 312, 320, 360, 400, 402, 404}},
+      {7, 7, false, {112, 784, 840, 896, 952, 952, 980, 1008, 1036, 1064, 1092, 1120, 1260, 1400, 1407, 1414}},
+      {1, 1, true, {16, 112, 120, 128, 136, 144, 148, 152, 156, 160, 164, 168, 188, 208, 209, 210}},
+      {2, 1, true, {16, 112, 128, 144, 160, 168, 176, 184, 192, 200, 208, 216, 256, 296, 298, 300}},
+      {2, 2, true, {32, 224, 240, 256, 272, 284, 292, 300, 308, 316, 324, 332, 372, 412, 414, 416}},
+      {7, 1, true, {16, 112, 168, 224, 280, 288, 316, 344, 372, 400, 428, 456, 596, 736, 743, 750}},
+      {7, 7, true, {112, 784, 840, 896, 952, 984, 1012, 1040, 1068, 1096, 1124, 1152, 1292, 1432, 1439, 1446}}};
+  for (const Want& w : want) {
+    const TextTables t = text_tables(w.m, w.nc, w.seq);
+    const uint64_t got[16] = {t.sha,   t.toff,  t.slot,  t.poff, t.first, t.tlen, t.cap, t.psize,
+                              t.osize, t.lines, t.flat,  t.exp,  t.dig,   t.fin,  t.ver, t.bytes};
+    CHECK(t.b64 == 0);
+    for (int k = 0; k < 16; ++k) CHECK(got[k] == w.at[k]);
+  }
 }
 
 int main() {
@@ -294,6 +348,8 @@ int main() {
   test_copyback();
   test_text_cutting();
   test_past_4gib();
+  test_checkers_agree();
+  test_table_offsets();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

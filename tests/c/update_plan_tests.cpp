@@ -5,6 +5,8 @@
 // plain g++ and again with -fsanitize=address,undefined and runs both.
 #include "update_plan.hpp"
 
+#include "check_cases.hpp"
+
 #include <cstdio>
 #include <cstring>
 
@@ -216,11 +218,85 @@ static void test_past_4gib() {
   CHECK(runs.size() == 3 && runs[1].src == G - 6 && runs[1].dst % 16 == (G - 6) % 16 && runs[2].src == G + 164);
 }
 
+// The one-piece and the seq checker over seeded calls (check_cases.hpp): each
+// answers what tests/golden/plan_checks.txt records of the checkers before the
+// planners were merged, and where no state repeats the two agree to the word.
+static void test_checkers_agree() {
+  using namespace plan_cases;
+  const std::vector<Recorded> want = read_fixture(fixture_path(__FILE__));
+  CHECK(want.size() == kCases);
+  if (want.size() != kCases) return;
+  uint64_t repeats = 0, refused = 0;
+  for (uint64_t k = 0; k < kCases; ++k) {
+    const Case c = make_case(k);
+    CHECK(checksum(c) == want[k].sum);
+    Answer one, seq;
+    one.piece = update_check(c.states.data(), c.n_states, c.so(), c.base_len, c.offsets.data(), c.sizes.data(), c.n,
+                             one.why);
+    seq.piece = update_seq_check(c.states.data(), c.n_states, c.so(), c.base_len, c.offsets.data(), c.sizes.data(),
+                                 nullptr, c.n, seq.why);
+    CHECK(one == want[k].hash_one);
+    CHECK(seq == want[k].hash_seq);
+    if (!c.repeats) CHECK(one == seq);
+    repeats += c.repeats;
+    refused += one.piece != kNoPiece;
+  }
+  CHECK(repeats > kCases / 4 && repeats < kCases / 2 && refused > kCases / 4);
+}
+
+// The one-piece calls' chain table: for ids of which none repeats, the identity equals the grouping.
+static void test_identity_table() {
+  const std::vector<std::vector<uint64_t>> cases = {{}, {0}, {7, 3, 9, 0}, {1ull << 32, 0, 5}, {4, 3, 2, 1, 0}};
+  for (const std::vector<uint64_t>& ids : cases) {
+    const ChainTable a = identity_table(ids), b = chain_table(ids);
+    CHECK(a.order == b.order && a.chain_id == b.chain_id && a.first == b.first && a.chains() == ids.size());
+  }
+  std::vector<uint64_t> many(1000);
+  for (size_t k = 0; k < many.size(); ++k) many[k] = (k * 7919) % 1000 + (k % 3 ? 0 : 1ull << 40);
+  const ChainTable a = identity_table(many), b = chain_table(many);
+  CHECK(a.order == b.order && a.chain_id == b.chain_id && a.first == b.first);
+  // by a launch's cuts: the state each cut's piece names, or the piece itself
+  const uint32_t so[3] = {5, 2, 9};
+  const std::vector<UpdateCut> cuts = {UpdateCut{2, 0, 8, true}, UpdateCut{0, 8, 8, true}};
+  CHECK((table_of(cuts, so, false).chain_id == std::vector<uint64_t>{9, 5}));
+  CHECK((table_of(cuts, nullptr, false).chain_id == std::vector<uint64_t>{2, 0}));
+  CHECK((table_of(cuts, so, true).chain_id == std::vector<uint64_t>{9, 5}));
+}
+
+// Where a hash launch's tables lie: the numbers of the hand-written offset
+// chains the layout replaced.  One piece per state: states (96 m) | offsets
+// (8 m) | sizes (4 m) | expected (20 m) | final flags (m).  Seq: states (96 nc)
+// | offsets (8 m) | chain_first (4 (nc + 1)) | sizes | expected | final flags.
+static void test_table_offsets() {
+  struct One { uint64_t m, off, size, exp, fin, bytes; };
+  const One one[3] = {{1, 96, 104, 108, 128, 129}, {2, 192, 208, 216, 256, 258}, {7, 672, 728, 756, 896, 903}};
+  for (const One& w : one) {
+    const HashTables t = hash_tables(w.m, w.m, false);
+    CHECK(t.states == 0 && t.off == w.off && t.size == w.size && t.exp == w.exp && t.fin == w.fin &&
+          t.bytes == w.bytes);
+  }
+  struct Seq { uint64_t m, nc, off, first, size, exp, fin, bytes; };
+  const Seq seq[5] = {{1, 1, 96, 104, 112, 116, 136, 137},
+                      {2, 1, 96, 112, 120, 128, 168, 170},
+                      {2, 2, 192, 208, 220, 228, 268, 270},
+                      {7, 1, 96, 152, 160, 188, 328, 335},
+                      {7, 7, 672, 728, 760, 788, 928, 935}};
+  for (const Seq& w : seq) {
+    const HashTables t = hash_tables(w.m, w.nc, true);
+    CHECK(t.states == 0 && t.off == w.off && t.first == w.first && t.size == w.size && t.exp == w.exp &&
+          t.fin == w.fin && t.bytes == w.bytes);
+  }
+  CHECK(round_up(0, 256) == 0 && round_up(1, 256) == 256 && round_up(256, 256) == 256 && round_up(257, 256) == 512);
+}
+
 int main() {
   test_refusals();
   test_cutting();
   test_runs();
   test_past_4gib();
+  test_checkers_agree();
+  test_identity_table();
+  test_table_offsets();
   if (g_fail) {
     std::fprintf(stderr, "%d check(s) failed\n", g_fail);
     return 1;

@@ -1,10 +1,10 @@
 // update_seq_plan_tests.cpp -- the planner of lbf_sha1_update_seq_batch and
-// lbf_b64_update_seq_batch (bitflood_amd/csrc/update_seq_plan.hpp) on the CPU:
+// lbf_b64_update_seq_batch (bitflood_amd/csrc/update_plan.hpp, b64_update_plan.hpp) on the CPU:
 // the stable grouping into a chain table, chains that straddle launches, every
 // refusal, and the text areas and copy-back ranges of a chain.  Includes only
-// that header and links nothing; tests/test_update_seq_cpu.py compiles it with
+// those headers and links nothing; tests/test_update_seq_cpu.py compiles it with
 // plain g++ and again with -fsanitize=address,undefined and runs both.
-#include "update_seq_plan.hpp"
+#include "b64_update_plan.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -64,11 +64,9 @@ static void test_grouping() {
   }
 }
 
-// The chain table of one launch's cuts, as update_seq_batch.cpp builds it.
+// The chain table of one launch's cuts, as update_batch.cpp builds it for the seq calls.
 static ChainTable table_of(const std::vector<UpdateCut>& cuts, const uint32_t* state_of) {
-  std::vector<uint64_t> ids;
-  for (const UpdateCut& c : cuts) ids.push_back(update_state_of(state_of, c.piece));
-  return chain_table(ids);
+  return table_of(cuts, state_of, true);
 }
 
 static void test_straddling() {
@@ -244,7 +242,7 @@ static void test_text_refusals() {
 static void one_chain(uint64_t decoded, uint32_t nc, uint32_t pieces, uint32_t len, uint32_t cap, uint64_t want_room) {
   std::vector<B64Place> places;
   const uint64_t chars = (uint64_t)pieces * len;
-  const uint64_t area = b64_update_seq_places({decoded}, {nc}, {chars}, {cap}, places);
+  const uint64_t area = b64_update_places({decoded}, {nc}, {chars}, {cap}, places);
   const uint64_t at = std::min<uint64_t>(decoded, cap);
   CHECK(places.size() == 1);
   CHECK(places[0].dev == at % 64);                 // the chain's position mod 64: the hash's aligned loop applies
@@ -267,7 +265,7 @@ static void test_text_areas() {
   one_chain(5, 0, 3, 0, 1000, 2);          // empty pieces
   // two chains in one launch follow one another, each at its position mod 64
   std::vector<B64Place> places;
-  const uint64_t area = b64_update_seq_places({3, 130}, {0, 1}, {8, 400}, {90, 1000}, places);
+  const uint64_t area = b64_update_places({3, 130}, {0, 1}, {8, 400}, {90, 1000}, places);
   CHECK(places[0].dev == 3 && places[0].room == 8);
   CHECK(places[1].dev >= places[0].dev + places[0].room && places[1].dev % 64 == 130 % 64 && places[1].dev < 11 + 64);
   CHECK(places[1].room == 3 * 100 + 2 && area == places[1].dev + places[1].room);
@@ -275,12 +273,12 @@ static void test_text_areas() {
   // copy-back: one range per chain (its pieces decode to adjacent bytes); chains whose ranges touch on both
   // sides travel as one run, a chain that got nothing takes none
   std::vector<Run> runs;
-  b64_update_copyback({places[0].dev, places[1].dev}, {1000 + 3, 5000 + 130}, {6, 300}, runs);
+  copyback_runs({places[0].dev, places[1].dev}, {1000 + 3, 5000 + 130}, {6, 300}, runs);
   CHECK(runs.size() == 2 && runs[0].src == 3 && runs[0].dst == 1003 && runs[0].len == 6);
   CHECK(runs[1].src == places[1].dev && runs[1].dst == 5130 && runs[1].len == 300);
-  b64_update_copyback({0, 64, 70}, {100, 200, 206}, {10, 6, 3}, runs);
+  copyback_runs({0, 64, 70}, {100, 200, 206}, {10, 6, 3}, runs);
   CHECK(runs.size() == 2 && runs[1].src == 64 && runs[1].len == 9);
-  b64_update_copyback({0, 64}, {100, 200}, {0, 0}, runs);
+  copyback_runs({0, 64}, {100, 200}, {0, 0}, runs);
   CHECK(runs.empty());
 }
 

@@ -123,7 +123,7 @@ def test_b64_update_kernel_has_no_scratch_and_no_spills(tmp_path):
     src = os.path.join(CSRC, "b64_update.hip")
     srcs = subprocess.run(["make", "-s", "-C", CSRC, "sources"], capture_output=True, text=True,
                           check=True).stdout.split()
-    assert "b64_update.hip" in srcs and "b64_update_batch.cpp" in srcs
+    assert "b64_update.hip" in srcs and "update_batch.cpp" in srcs
     r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
                         "-I" + CSRC, "--offload-device-only", "-c", "-o", str(tmp_path / "u.o"),
                         "-Rpass-analysis=kernel-resource-usage", src], capture_output=True, text=True)

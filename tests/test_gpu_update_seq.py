@@ -16,7 +16,8 @@ import hashlib
 import numpy as np
 import pytest
 
-from bitflood_amd import STATE_DTYPE, DeviceBuffer, LbfError, _capi, chain_table, new_states
+from bitflood_amd import (STATE_DTYPE, DeviceBuffer, LbfError, _capi, chain_table, new_b64_states,
+                          new_states)
 from bitflood_amd import hashing as H
 from tests import sha1_model
 from tests import wire_piece_model as M
@@ -547,3 +548,73 @@ def test_chain_table_drives_the_launch():
               for c, s in enumerate(chain_state)]
     assert [s for s, _ in chains] == [3, 1, 0]
     run_launch(chains, 4, phase=1)
+
+
+def test_one_piece_and_seq_calls_agree_over_cut_pieces_and_launches(monkeypatch):
+    """The calls that take one piece per state and the seq calls, given the same
+    pieces with no state repeated, through launches that multiply and a piece
+    that is cut: states after each call, digests, verdicts, and for text the
+    slots and lengths, are equal between the two and to hashlib.  Five chains of
+    0, 1, 63, 64 and 200 bytes, two calls per chain, the second final with
+    expected digests of which one is wrong.  A context's launches hold 1 MiB at
+    the least (LBF_UPDATE_MB=1), so a sixth chain brings a piece of 1 MiB + 200
+    bytes: it is cut, and every call is several launches."""
+    from bitflood_amd import ChunkHasher
+    from tests import wire_layouts as W
+    monkeypatch.setenv("LBF_UPDATE_MB", "1")
+    rng = np.random.default_rng(77)
+    first = [0, 1, 63, 64, 200, (1 << 20) + 200]
+    second = [1, 63, 64, 200, 0, 77]
+    state_of = [3, 0, 4, 1, 5, 2]  # no state repeats
+    n = len(first)
+    calls = [[rnd(rng, s) for s in first], [rnd(rng, s) for s in second]]
+    arena = Arena(3)
+    offs = [[arena.put(p) for p in call] for call in calls]
+    buf = arena.buffer()
+    whole = [calls[0][k] + calls[1][k] for k in range(n)]
+    expected = np.array([np.frombuffer(sha1(w), dtype=np.uint8) for w in whole])
+    expected[2, 7] ^= 0x10  # one digest is wrong
+    mid = {state_of[k]: sha1_model.update(sha1_model.init(), calls[0][k]) for k in range(n)}
+    with ChunkHasher(device_mask=1) as h:
+        results = []
+        for fn in ("lbf_sha1_update_batch", "lbf_sha1_update_seq_batch"):
+            st = new_states(n)
+            dig = np.full((n, 20), FILL, dtype=np.uint8)
+            ver = np.full(n, FILL, dtype=np.uint8)
+            assert raw_batch(h, fn, st, buf, offs[0], first, state_of, None, None, None, None) == 0
+            check_states(st, n, mid, new_states(n))
+            after_first = st.tobytes()
+            assert raw_batch(h, fn, st, buf, offs[1], second, state_of, [1] * n, dig, expected, ver) == 0
+            assert [bytes(d) for d in dig] == [sha1(w) for w in whole], fn
+            assert ver.tolist() == [1, 1, 0, 1, 1, 1], fn
+            assert st.tobytes() == new_states(n).tobytes()
+            results.append((after_first, dig.tobytes(), ver.tobytes()))
+        assert results[0] == results[1]
+
+        # text: chunks of 0, 57 and 130 bytes in the encoder's layout, and one whose text is larger than a launch
+        chunks = [b"", rnd(rng, 57), rnd(rng, 130), rnd(rng, 800000)]
+        texts = [W.xmlrpc_text(c) for c in chunks]
+        assert len(texts[3]) > (1 << 20)
+        slots = np.concatenate([[5], 5 + np.cumsum([len(c) + 3 for c in chunks])[:-1]]).astype(np.uint64)
+        caps = [len(c) for c in chunks]
+        exp = np.array([np.frombuffer(sha1(c), dtype=np.uint8) for c in chunks])
+        exp[1, 0] ^= 1  # one digest is wrong
+        want = np.full(int(slots[-1]) + caps[-1] + 9, FILL, dtype=np.uint8)
+        for c, s in zip(chunks, slots):
+            want[int(s):int(s) + len(c)] = np.frombuffer(c, dtype=np.uint8)
+        for split in (1, 74):
+            runs = []
+            for fn in (h.update_text, h.update_text_seq):
+                b64, sha, out = new_b64_states(4), new_states(4), np.full_like(want, FILL)
+                stages = []
+                for final, pieces in ((0, [t[:split] for t in texts]), (1, [t[split:] for t in texts])):
+                    lens = [len(p) for p in pieces]
+                    toff = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
+                    sizes, ver = fn(b64, sha, np.frombuffer(b"".join(pieces) + b"\0", dtype=np.uint8), toff, lens, out,
+                                    slots, caps, state_of=[2, 0, 3, 1], final=[final] * 4, expected=exp)
+                    stages.append((b64.tobytes(), sha.tobytes(), out.tobytes(), sizes.tolist(), ver.tolist()))
+                assert stages[0][3] == [0] * 4 and stages[0][4] == [False] * 4
+                assert stages[1][3] == caps and stages[1][4] == [True, False, True, True], split
+                assert stages[1][2] == want.tobytes(), split
+                runs.append(stages)
+            assert runs[0] == runs[1], split

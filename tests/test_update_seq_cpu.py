@@ -1,6 +1,6 @@
 """Several pieces of one chain per call, the parts that need no GPU: the
 exported symbols and bindings, chain_table, the batch calls' planner
-(bitflood_amd/csrc/update_seq_plan.hpp, by tests/c/update_seq_plan_tests.cpp,
+(bitflood_amd/csrc/update_plan.hpp and b64_update_plan.hpp, by tests/c/update_seq_plan_tests.cpp,
 plain and under ASan/UBSan as stand-alone programs), and the two new kernels'
 resource usage on gfx950 (no scratch, no spills, no dynamic stack)."""
 import os
@@ -97,7 +97,7 @@ def _build_plan_tests(tmp_path, name, extra):
                                         ("asan_ubsan", ["-fsanitize=address,undefined", "-fno-omit-frame-pointer"])])
 def test_update_seq_plan_program(tmp_path, name, extra):
     """Grouping, straddling chains, every refusal, text areas and copy-back
-    ranges of update_seq_plan.hpp, as a stand-alone program (no preload, no
+    ranges of the seq calls' planner, as a stand-alone program (no preload, no
     Python under a sanitizer)."""
     exe = _build_plan_tests(tmp_path, "update_seq_plan_tests_" + name, extra)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
@@ -107,7 +107,7 @@ def test_update_seq_plan_program(tmp_path, name, extra):
 
 
 def test_update_seq_plan_header_is_hip_free():
-    for name in ("update_seq_plan.hpp", "update_plan.hpp", "b64_update_plan.hpp", "stage_plan.hpp"):
+    for name in ("update_plan.hpp", "b64_update_plan.hpp", "stage_plan.hpp"):
         text = open(os.path.join(CSRC, name)).read()
         assert "hip/" not in text and "lbf_internal.hpp" not in text and "lbf_host.hpp" not in text, name
 
