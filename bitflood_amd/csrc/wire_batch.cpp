@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "b64_flat.hpp"
+#include "b64_flat_encode.hpp"
 #include "lbf_host.hpp"
 
 using namespace lbf;
@@ -41,42 +42,44 @@ constexpr uint64_t kB64MaxChunk = 1ull << 30, kB64MaxText = 3ull << 29;
 
 extern "C" uint64_t lbf_b64_put_length(uint64_t size) { return 4 * (size / 3) + (size % 3 ? 4 : 0) + size / 3 / 18; }
 
+namespace {
+
 // Chunks to send: verify on the device (ChunkMethods.cpp:116-123), then encode
-// each as the base64 text of its SendChunk frame (XmlRpcValue.cpp:439-452,
-// kern_b64.hpp), from the same
-// device copy.  Synchronous on worker 0's first stream: one H2D of the bytes'
-// span and one of the tables, two launches, one D2H of the verdicts and one of
-// the text span.
-extern "C" int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len,
-                                           const uint64_t* offsets, const uint32_t* sizes, uint64_t n,
-                                           const uint8_t* expected, uint8_t* verdicts, char* text, uint64_t text_len,
-                                           const uint64_t* text_offsets) {
+// each as the base64 text of its SendChunk frame from the same device copy, in
+// xmlrpc++'s lines (XmlRpcValue.cpp:439-452, kern_b64.hpp) or unbroken, as the
+// Java and Perl peers write it (b64_flat_encode.hip).  Synchronous on worker
+// 0's first stream: one H2D of the bytes' span and one of the tables, two
+// launches, one D2H of the verdicts and one per run of text slots.  `who` names
+// the entry point in the refusals.
+int verify_encode_b64(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, const uint64_t* offsets,
+                      const uint32_t* sizes, uint64_t n, const uint8_t* expected, uint8_t* verdicts, int layout,
+                      char* text, uint64_t text_len, const uint64_t* text_offsets, const std::string& who) {
+  if (layout != LBF_B64_LAYOUT_XMLRPC && layout != LBF_B64_LAYOUT_FLAT)
+    return fail(LBF_ERR_INVALID, who + ": layout is neither LBF_B64_LAYOUT_XMLRPC nor LBF_B64_LAYOUT_FLAT");
+  if (n != 0 && (!data || !offsets || !sizes || !expected || !verdicts || !text || !text_offsets))
+    return fail(LBF_ERR_INVALID, who + ": null argument");
   if (!ctx) return fail(LBF_ERR_INVALID, "null context");
   if (n == 0) return LBF_OK;
-  if (!data || !offsets || !sizes || !expected || !verdicts || !text || !text_offsets)
-    return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: null argument");
-  if (n > 0x7FFFFFFFull) return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: n too large");
+  if (n > 0x7FFFFFFFull) return fail(LBF_ERR_INVALID, who + ": n too large");
   uint64_t dlo = UINT64_MAX, dhi = 0, tlo = UINT64_MAX, thi = 0;
+  std::vector<uint64_t> tlens(n);
+  uint32_t max_size = 0;
   for (uint64_t i = 0; i < n; ++i) {
     if (sizes[i] > kB64MaxChunk)
-      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: chunk " + std::to_string(i) +
-                                       " larger than the wire encode takes (1 GiB)");
+      return fail(LBF_ERR_INVALID, who + ": chunk " + std::to_string(i) + " larger than the wire encode takes (1 GiB)");
     if (offsets[i] > data_len || sizes[i] > data_len - offsets[i])
-      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: chunk " + std::to_string(i) + " outside the buffer");
-    const uint64_t tl = lbf_b64_put_length(sizes[i]);
+      return fail(LBF_ERR_INVALID, who + ": chunk " + std::to_string(i) + " outside the buffer");
+    const uint64_t tl = tlens[i] = lbf_b64_text_length(sizes[i], layout);
     if (text_offsets[i] > text_len || tl > text_len - text_offsets[i])
-      return fail(LBF_ERR_INVALID, "lbf_verify_encode_b64_batch: text slot " + std::to_string(i) + " outside the buffer");
+      return fail(LBF_ERR_INVALID, who + ": text slot " + std::to_string(i) + " outside the buffer");
     dlo = std::min(dlo, offsets[i]);
     dhi = std::max(dhi, offsets[i] + sizes[i]);
     tlo = std::min(tlo, text_offsets[i]);
     thi = std::max(thi, text_offsets[i] + tl);
+    max_size = std::max(max_size, sizes[i]);
   }
-  uint32_t max_size = 0;
-  for (uint64_t i = 0; i < n; ++i) max_size = std::max(max_size, sizes[i]);
-  std::vector<uint64_t> tlens(n);
-  for (uint64_t i = 0; i < n; ++i) tlens[i] = lbf_b64_put_length(sizes[i]);
   std::vector<SlotRun> runs;  // the text slots the D2H writes, and nothing between them
-  if (int rc = checked_slot_runs(text_offsets, tlens.data(), n, "lbf_verify_encode_b64_batch", runs)) return rc;
+  if (int rc = checked_slot_runs(text_offsets, tlens.data(), n, who.c_str(), runs)) return rc;
   dlo &= ~15ull;  // device offsets keep the host offsets' alignment mod 16
   tlo &= ~15ull;
   return guarded([&] {
@@ -97,7 +100,7 @@ extern "C" int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, ui
     KeepCurrentDevice keep;
     Worker& w = ctx->workers[0];
     LBF_HIP_TRY(hipSetDevice(w.device));
-    if (int rc = b64_scratch(ctx, need, "lbf_verify_encode_b64_batch")) return rc;
+    if (int rc = b64_scratch(ctx, need, who.c_str())) return rc;
     uint8_t* d_data = ctx->b64_dev;
     uint8_t* d_text = d_data + data_b;
     uint8_t* d_in = d_text + text_b;
@@ -111,13 +114,35 @@ extern "C" int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, ui
     const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_toff + n);
     const uint8_t* d_exp = reinterpret_cast<const uint8_t*>(d_sz + n);
     if (int rc = lbf_sha1_launch(d_data, d_doff, d_sz, n, nullptr, d_exp, d_ver, st)) return rc;
-    if (int rc = lbf::launch_b64_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st)) return rc;
+    if (int rc = layout == LBF_B64_LAYOUT_FLAT
+                     ? lbf::launch_b64_flat_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st)
+                     : lbf::launch_b64_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st))
+      return rc;
     LBF_HIP_TRY(hipMemcpyAsync(verdicts, d_ver, n, hipMemcpyDeviceToHost, st));
     for (const SlotRun& r : runs)
       LBF_HIP_TRY(hipMemcpyAsync(text + r.lo, d_text + (r.lo - tlo), r.hi - r.lo, hipMemcpyDeviceToHost, st));
     LBF_HIP_TRY(hipStreamSynchronize(st));
     return (int)LBF_OK;
   });
+}
+
+}  // namespace
+
+extern "C" int lbf_verify_encode_b64_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len,
+                                           const uint64_t* offsets, const uint32_t* sizes, uint64_t n,
+                                           const uint8_t* expected, uint8_t* verdicts, char* text, uint64_t text_len,
+                                           const uint64_t* text_offsets) {
+  if (!ctx) return fail(LBF_ERR_INVALID, "null context");  // this call's first refusal, as it has always been
+  return verify_encode_b64(ctx, data, data_len, offsets, sizes, n, expected, verdicts, LBF_B64_LAYOUT_XMLRPC, text,
+                           text_len, text_offsets, "lbf_verify_encode_b64_batch");
+}
+
+extern "C" int lbf_verify_encode_b64_layout_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len,
+                                                  const uint64_t* offsets, const uint32_t* sizes, uint64_t n,
+                                                  const uint8_t* expected, uint8_t* verdicts, int layout, char* text,
+                                                  uint64_t text_len, const uint64_t* text_offsets) {
+  return verify_encode_b64(ctx, data, data_len, offsets, sizes, n, expected, verdicts, layout, text, text_len,
+                           text_offsets, "lbf_verify_encode_b64_layout_batch");
 }
 
 namespace {

@@ -548,11 +548,13 @@ class ChunkHasher:
                                              ver.ctypes.data))
         return ver.astype(bool), sizes
 
-    def verify_encode_b64(self, data, offsets, sizes, expected):
+    def verify_encode_b64(self, data, offsets, sizes, expected, layout="xmlrpc"):
         """The sender's verify + encode on the device
-        (lbf_verify_encode_b64_batch, ChunkMethods.cpp:89-135 with xmlrpc++'s
-        base64 encode): chunk i = data[offsets[i], + sizes[i]).  Returns
-        (verdicts as bool, [text of chunk i as bytes])."""
+        (lbf_verify_encode_b64_layout_batch, ChunkMethods.cpp:89-135 with the
+        base64 encode of `layout`: "xmlrpc", xmlrpc++'s lines, or "flat", the
+        unbroken text of the Java and Perl peers): chunk i = data[offsets[i], +
+        sizes[i]).  Returns (verdicts as bool, [text of chunk i as bytes])."""
+        lay = _layout(layout)
         buf = _as_u8(data)
         offs = np.ascontiguousarray(offsets, dtype=np.uint64)
         sz = np.ascontiguousarray(sizes, dtype=np.uint32)
@@ -563,7 +565,7 @@ class ChunkHasher:
         ver = np.zeros(n, dtype=np.uint8)
         if n == 0:
             return ver.astype(bool), []
-        lens = [int(self._lib.lbf_b64_put_length(int(s))) for s in sz]
+        lens = [int(self._lib.lbf_b64_text_length(int(s), lay)) for s in sz]
         toff = np.zeros(n, dtype=np.uint64)
         pos = 0
         for i, tl in enumerate(lens):
@@ -571,9 +573,9 @@ class ChunkHasher:
             pos += (tl + 15) // 16 * 16
         text = np.zeros(max(pos, 1), dtype=np.uint8)
         base = buf.ctypes.data if buf.size else ctypes.addressof(_EMPTY)
-        check(self._lib.lbf_verify_encode_b64_batch(self._h, base, buf.size, offs.ctypes.data, sz.ctypes.data, n,
-                                                    exp.ctypes.data, ver.ctypes.data, text.ctypes.data, text.size,
-                                                    toff.ctypes.data))
+        check(self._lib.lbf_verify_encode_b64_layout_batch(self._h, base, buf.size, offs.ctypes.data, sz.ctypes.data,
+                                                           n, exp.ctypes.data, ver.ctypes.data, lay, text.ctypes.data,
+                                                           text.size, toff.ctypes.data))
         return ver.astype(bool), [text[int(toff[i]):int(toff[i]) + lens[i]].tobytes() for i in range(n)]
 
     def sha1(self, data) -> bytes:
@@ -715,6 +717,17 @@ def b64_encode_update_launch(enc_states, sha_states, n_states, state_of, base, o
                                               p(expected), p(verdicts), stream))
 
 
+def verify_encode_b64_launch(base, offsets, sizes, n, max_size, text, text_offsets, layout="xmlrpc", digests=None,
+                             expected=None, verdicts=None, stream=None):
+    """lbf_verify_encode_b64_launch: chunks in device memory hashed (digests
+    and/or expected + verdicts; with none of them the call only encodes) and
+    encoded into their text slots in one layout, asynchronous on `stream`;
+    max_size is the largest chunk and sizes the grids."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_verify_encode_b64_launch(p(base), p(offsets), p(sizes), n, max_size, p(digests), p(expected),
+                                              p(verdicts), _layout(layout), p(text), p(text_offsets), stream))
+
+
 def set_b64_lines(on) -> bool:
     """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
     off, process-wide; returns the previous setting."""
@@ -747,6 +760,7 @@ def set_kernel_variant(v: int):
 __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode", "chunk_table",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
            "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "B64_ENC_STATE_DTYPE", "new_b64_enc_states",
-           "b64_text_length", "b64_encode_update_launch", "chain_table", "update_seq_launch", "b64_update_seq_launch",
+           "b64_text_length", "b64_encode_update_launch", "verify_encode_b64_launch",
+           "chain_table", "update_seq_launch", "b64_update_seq_launch",
            "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

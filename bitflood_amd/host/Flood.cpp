@@ -358,15 +358,23 @@ Error::ErrorCode Flood::VerifyChunks(const U8* i_arena, U64 i_arena_len, const s
 
 // ChunkMethods.cpp:116-123 and the encode of its SendChunk payload
 // (XmlRpcValue::binaryToXml), both on the GPU from one device copy: chunk k's
-// base64 text lands at o_text + i_text_offsets[k] (lbf_b64_put_length of its
-// size) whatever its verdict.  Chunks VerifyChunks would skip stay '0' and get
-// no text.
+// base64 text lands at o_text + i_text_offsets[k] (lbf_b64_text_length of its
+// size in the layout) whatever its verdict.  Chunks VerifyChunks would skip
+// stay '0' and get no text.
 Error::ErrorCode Flood::VerifyEncodeChunks(const U8* i_arena, U64 i_arena_len, const std::vector<ChunkArrival>& i_chunks,
                                            std::string& o_valid, char* o_text, U64 i_text_len,
                                            const V_U64& i_text_offsets) {
+  return VerifyEncodeChunks(i_arena, i_arena_len, i_chunks, o_valid, o_text, i_text_len, i_text_offsets,
+                            LBF_B64_LAYOUT_XMLRPC);
+}
+
+Error::ErrorCode Flood::VerifyEncodeChunks(const U8* i_arena, U64 i_arena_len, const std::vector<ChunkArrival>& i_chunks,
+                                           std::string& o_valid, char* o_text, U64 i_text_len,
+                                           const V_U64& i_text_offsets, int i_layout) {
   const size_t n = i_chunks.size();
   o_valid.assign(n, '0');
   if (i_text_offsets.size() != n) return Error::UNKNOWN_ERROR_LBF;
+  if (i_layout != LBF_B64_LAYOUT_XMLRPC && i_layout != LBF_B64_LAYOUT_FLAT) return Error::UNKNOWN_ERROR_LBF;
   V_U64 voff, toff;
   V_U32 vsz;
   V_U8 vexp;
@@ -378,7 +386,7 @@ Error::ErrorCode Flood::VerifyEncodeChunks(const U8* i_arena, U64 i_arena_len, c
     const FloodFile::Chunk& c = it->second.m_file->m_chunks[a.m_index];
     if (c.m_size != a.m_size) continue;
     if (a.m_offset > i_arena_len || a.m_size > i_arena_len - a.m_offset) continue;
-    const U64 tl = lbf_b64_put_length(a.m_size);
+    const U64 tl = lbf_b64_text_length(a.m_size, i_layout);
     if (i_text_offsets[k] > i_text_len || tl > i_text_len - i_text_offsets[k]) continue;
     U8 e[20];
     if (!decode_hash(c.m_hash, e)) continue;
@@ -394,8 +402,9 @@ Error::ErrorCode Flood::VerifyEncodeChunks(const U8* i_arena, U64 i_arena_len, c
   if (!ctx) return Error::UNKNOWN_ERROR_LBF;
   std::vector<U8> verdict(which.size(), 0);
   static const U8 kEmpty = 0;
-  if (lbf_verify_encode_b64_batch(ctx, i_arena_len ? i_arena : &kEmpty, i_arena_len, &voff[0], &vsz[0], which.size(),
-                                  &vexp[0], &verdict[0], o_text, i_text_len, &toff[0]) != LBF_OK)
+  if (lbf_verify_encode_b64_layout_batch(ctx, i_arena_len ? i_arena : &kEmpty, i_arena_len, &voff[0], &vsz[0],
+                                         which.size(), &vexp[0], &verdict[0], i_layout, o_text, i_text_len,
+                                         &toff[0]) != LBF_OK)
     return Error::UNKNOWN_ERROR_LBF;
   for (size_t j = 0; j < which.size(); ++j)
     if (verdict[j]) o_valid[which[j]] = '1';

@@ -24,8 +24,9 @@
 // With --corrupt K the seeder flips one byte of every K-th chunk AFTER its own
 // verify (a wire error); the leecher must reject it and ask again.
 // With --wire-layout flat the seeder frames every chunk as unbroken base64, as
-// bitflood's Java and Perl peers do (a host-side encode; the default, xmlrpc,
-// is xmlrpc++'s 73-character lines).  The leecher takes either; its line
+// bitflood's Java and Perl peers do (a host-side encode, or with --gpu-encode
+// the GPU's, Flood::VerifyEncodeChunks with LBF_B64_LAYOUT_FLAT; the default,
+// xmlrpc, is xmlrpc++'s 73-character lines).  The leecher takes either; its line
 // reports the chunks its flat pass decoded (LBF_B64_FLAT=1 switches that on).
 // With --synthetic the seeder holds no file: its chunk bytes come from the
 // counter-mode generator (the stream lbf_fill_synthetic writes), re-verified on
@@ -102,7 +103,8 @@ struct Opts {
   bool gpu_decode = true;        // the leecher's base64 decode on the GPU with its verify (--cpu-decode: on the host)
   bool gpu_encode = false;       // --gpu-encode: the seeder's base64 encode on the GPU with its verify (--synthetic)
   bool wire_flat = false;        // --wire-layout flat: the seeder frames chunks as unbroken base64, as a Java or Perl
-                                 // seeder would (a host-side encode; the default, xmlrpc, is xmlrpc++'s lines)
+                                 // seeder would (on the host, or on the GPU with --gpu-encode; the default, xmlrpc,
+                                 // is xmlrpc++'s lines)
   unsigned seeder_workers = 1;   // --seeder-workers S: the seeder's verify/encode workers (each its own context)
   enum Role { BOTH, SEEDER, LEECHER } role = BOTH;  // --role: both peers in this process, or one of them
   int port = -1;                 // seeder: port to listen on (0 / unset = any); leecher: port to dial
@@ -519,6 +521,8 @@ void seeder_main(int lfd, FloodFileSPtr ff, std::string root, const Opts& o, See
   const U64 synth_cap = (slot_bytes * o.batch + page - 1) / page * page;
   // --gpu-encode: each arena's chunks come back from the GPU as base64 text,
   // one 16-byte aligned slot per chunk, in a text arena of its own
+  // (room for the longer of the two layouts' texts; --wire-layout flat asks the GPU for the unbroken one)
+  const int wire_layout = o.wire_flat ? LBF_B64_LAYOUT_FLAT : LBF_B64_LAYOUT_XMLRPC;
   const U64 text_slot = (PeerWire::Base64PutLength(o.chunksize) + 15) & ~15ull;
   const U64 text_cap = o.gpu_encode ? (text_slot * o.batch + page - 1) / page * page : 0;
   const unsigned pool_threads = std::max(1u, o.threads / o.seeder_workers);
@@ -592,13 +596,13 @@ void seeder_main(int lfd, FloodFileSPtr ff, std::string root, const Opts& o, See
         if (v.valid[k] != '1') return;  // "send only if equal" (ChunkMethods.cpp:117-123)
         if (o.gpu_encode) {  // the GPU's text; a wire error flips one of its characters
           const char* t = text_mem + v.arena * text_cap + v.toffs[k];
-          const size_t tl = PeerWire::Base64PutLength(sizes[k]);
+          const size_t tl = (size_t)lbf_b64_text_length(sizes[k], wire_layout);
           if (!flip[k]) {
             out[k] = PeerWire::FrameSendChunkText(keys[k].first, keys[k].second, t, tl);
             return;
           }
           std::string tmp(t, tl);
-          const size_t g = sizes[k] / 2 / 3, at = 4 * g + g / 18;  // a character of the middle byte's group
+          const size_t g = sizes[k] / 2 / 3, at = 4 * g + (o.wire_flat ? 0 : g / 18);  // of the middle byte's group
           tmp[at] = tmp[at] == 'A' ? 'B' : 'A';
           out[k] = PeerWire::FrameSendChunkText(keys[k].first, keys[k].second, tmp.data(), tl);
           return;
@@ -670,7 +674,7 @@ void seeder_main(int lfd, FloodFileSPtr ff, std::string root, const Opts& o, See
           v.toffs.resize(keys.size());
           for (size_t k = 0; k < keys.size(); ++k) v.toffs[k] = k * text_slot;
           if (fl.VerifyEncodeChunks(arena, synth_cap, chunks, v.valid, text_mem + v.arena * text_cap, text_cap,
-                                    v.toffs) != Error::NO_ERROR_LBF)
+                                    v.toffs, wire_layout) != Error::NO_ERROR_LBF)
             die("seeder: verify + encode failed: " + std::string(Encoder::LastError()));
         } else if (fl.VerifyChunks(arena, synth_cap, chunks, v.valid) != Error::NO_ERROR_LBF) {
           die("seeder: verify failed: " + std::string(Encoder::LastError()));
@@ -787,7 +791,6 @@ int main(int argc, char** argv) {
   if (o.chunksize == 0 || o.window == 0 || o.batch == 0) die("chunksize, window and batch must be > 0");
   if (o.verifiers == 0 || o.verifiers > 8) die("verifiers must be 1..8");
   if (o.seeder_workers == 0 || o.seeder_workers > 8) die("seeder workers must be 1..8");
-  if (o.gpu_encode && o.wire_flat) die("--wire-layout flat is a host-side encode: not with --gpu-encode");
   if (o.gpu_encode && !o.synthetic) die("--gpu-encode needs --synthetic (the file seeder reads and verifies in one call)");
   if (o.role != Opts::BOTH && o.dir.empty()) die("--role seeder/leecher needs --dir (the directory both peers share)");
   if (o.role == Opts::LEECHER && (o.port <= 0 || o.port > 65535)) die("--role leecher needs --port");
@@ -857,14 +860,16 @@ int main(int argc, char** argv) {
     close(lfd);
     printf("{\"config\": \"C5 loopback 2-peer\", \"role\": \"seeder\", \"pid\": %d, \"bytes\": %llu, "
            "\"chunk_size\": %u, \"chunks\": %zu, \"batch\": %u, \"seeder_pipelined\": %s, \"gpu_encode\": %s, "
+           "\"wire_layout\": \"%s\", "
            "\"seeder_workers\": %u, \"threads\": %u, \"seconds\": %.3f, \"encode_flood_s\": %.3f, "
            "\"seeder\": {\"requests\": %llu, \"sent\": %llu, \"refused\": %llu, \"verify_s\": %.3f, "
            "\"encode_s\": %.3f}, \"corrupt_every\": %u, \"corrupted_sent\": %llu, \"seed_source\": \"%s\", "
            "\"arenas_registered\": %s}\n",
            (int)getpid(), (unsigned long long)o.size, o.chunksize,
            ff->m_files.empty() ? (size_t)0 : ff->m_files.begin()->second->m_chunks.size(), o.batch,
-           o.seeder_pipeline ? "true" : "false", o.gpu_encode ? "true" : "false", o.seeder_workers, o.threads,
-           serve_s, encode_s, (unsigned long long)sst.requests, (unsigned long long)sst.sent,
+           o.seeder_pipeline ? "true" : "false", o.gpu_encode ? "true" : "false", o.wire_flat ? "flat" : "xmlrpc",
+           o.seeder_workers, o.threads, serve_s, encode_s, (unsigned long long)sst.requests,
+           (unsigned long long)sst.sent,
            (unsigned long long)sst.refused, sst.verify_s, sst.encode_s, o.corrupt, (unsigned long long)sst.corrupted,
            o.synthetic ? "synthetic stream (generated on request, no seeder file)" : "file",
            o.register_arenas ? "true" : "false");

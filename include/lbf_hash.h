@@ -628,6 +628,46 @@ int lbf_b64_encode_update_batch(lbf_ctx* ctx, lbf_b64_enc_state* enc_states, lbf
                                 uint64_t text_len, const uint64_t* text_offsets, const uint32_t* text_caps,
                                 uint64_t* new_offsets, uint32_t* new_lens, uint32_t* text_sizes);
 
+/* ---- chunks to send, one-shot, in either peer's text layout ---------------
+ * lbf_verify_encode_b64_batch with the layout of the text as an argument, one
+ * layout per call (a seeder with peers of both kinds makes two calls): chunk
+ * i = data[offsets[i], + sizes[i]) (host memory), verdicts[i] = 1 when its
+ * SHA-1 equals expected[20*i .. 20*i+20), and its text lands at
+ * text[text_offsets[i], + lbf_b64_text_length(sizes[i], layout)) whatever the
+ * verdict -- xmlrpc++'s lines for LBF_B64_LAYOUT_XMLRPC, byte for byte what
+ * lbf_verify_encode_b64_batch writes; for LBF_B64_LAYOUT_FLAT the unbroken
+ * RFC 4648 text bitflood's Java and Perl peers write
+ * (XMLEnvelopeProcessor.java:124, RPC/XML.pm:638): 4 * ceil(size / 3)
+ * characters, "xx==" / "xxx=" for a last one or two bytes and nothing else.
+ * No byte of `text` outside the slots is written.  Refused with
+ * LBF_ERR_INVALID: any other layout, a chunk outside [data, data + data_len),
+ * a slot outside [text, text + text_len), overlapping slots, a chunk of more
+ * than 1 GiB.  Synchronous, on the context's first device. */
+int lbf_verify_encode_b64_layout_batch(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, const uint64_t* offsets,
+                                       const uint32_t* sizes, uint64_t n, const uint8_t* expected, uint8_t* verdicts,
+                                       int layout, char* text, uint64_t text_len, const uint64_t* text_offsets);
+/* The same for chunks resident in device memory, asynchronous on `stream`:
+ * lbf_sha1_launch (the usual kernel selection) followed by the layout's encode
+ * kernel and one small kernel, no host round trip and no device allocation.
+ * Chunk i = d_data[d_offsets[i], + d_sizes[i]); its text lands at
+ * d_text[d_text_offsets[i], + lbf_b64_text_length(d_sizes[i], layout)), and no
+ * other byte of d_text is written, so slots may be packed next to one another
+ * at any byte phase.  d_digests, or d_expected / d_verdicts (which go
+ * together), may be NULL; with all three NULL the call only encodes.  The host
+ * cannot read d_sizes, so max_size -- the largest chunk of the call, at most
+ * 1 GiB -- sizes the grids.  A chunk with d_sizes[i] > max_size is a caller
+ * error that stays defined: nothing outside its slot is written, its text is
+ * incomplete, and d_verdicts[i] (when given) is cleared; its digest is still
+ * its bytes'.  Two slots that overlap are undefined but memory-safe (the batch
+ * call refuses them).  Refused with LBF_ERR_INVALID before anything is
+ * enqueued: a layout other than the two LBF_B64_LAYOUT_* values, max_size over
+ * 1 GiB, a NULL d_data, d_offsets, d_sizes, d_text or d_text_offsets, n over
+ * 2^31-1, a table that is not aligned to its element size or does not fit the
+ * allocation it points into.  n == 0 returns LBF_OK and enqueues nothing. */
+int lbf_verify_encode_b64_launch(const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t n,
+                                 uint32_t max_size, uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
+                                 int layout, char* d_text, const uint64_t* d_text_offsets, void* stream);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */
