@@ -14,12 +14,15 @@
 // The kernel lays tiles of whole lines over the CHUNK's text (not the piece's),
 // so that 16-byte text blocks fall at the same places for every cut: a block
 // wholly inside the piece's characters is one 16-byte store, the ragged ends go
-// byte by byte.  The block window is the one-shot encode's (b64_encode_tile),
-// restated here: that header belongs to sha1_kernels.hip's translation unit,
-// whose ISA stays as recorded (tests/test_isa.py).  DESIGN.md §4.8.
+// byte by byte.  The staging, the block store, the alphabet and a group's
+// characters are b64_device.hpp's; the five-word window of a line's block is the
+// one-shot encode's (b64_encode_tile, kern_b64.hpp), written out in both: as a
+// shared function it changes both kernels' recorded ISA (tests/test_isa.py).
+// DESIGN.md §4.8.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "b64_device.hpp"
 #include "b64_encode_update.hpp"
 #include "lbf_internal.hpp"
 
@@ -51,8 +54,6 @@ struct EncUpdParams {
   uint8_t* verdicts;           // cleared for a final piece whose text does not fit; may be null
 };
 
-typedef uint32_t enc_u32x4 __attribute__((ext_vector_type(4)));
-
 // LDS: one block in front of the staged span (the carried bytes go right below
 // the piece's first byte), the span's aligned blocks (a tile's bytes at any
 // 16-byte phase: one block more than the tile), and slack for the group reads of
@@ -64,37 +65,8 @@ constexpr uint32_t kPer = (kSpanBlocks + kEncUpdThreads - 1) / kEncUpdThreads;  
 // the last window reads group kEncUpdTileGroups + 4: eight bytes from 3 * that, behind front and phase
 static_assert(kFront + 15 + 3 * (kEncUpdTileGroups + 4) + 8 <= 16 * kStageBlocks, "the window stays inside the stage");
 
-// Global bytes [src, src + len) as the aligned 16-byte blocks that hold them,
-// to LDS from byte kFront on: afterwards lds byte (kFront + delta + k) = src[k].
-// An empty span loads nothing (its address may be the end of an allocation).
-struct EncStage {
-  enc_u32x4 v[kPer];
-  uint32_t blocks = 0, delta = 0;
-  __device__ __forceinline__ void load(const uint8_t* src, uint32_t len) {
-    blocks = 0;
-    delta = 0;
-    if (len == 0) return;
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    delta = (uint32_t)(a & 15u);
-    const enc_u32x4* g = reinterpret_cast<const enc_u32x4*>(a - delta);
-    blocks = (delta + len + 15) / 16;
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kEncUpdThreads < blocks)
-        v[k] = __builtin_nontemporal_load(g + threadIdx.x + k * kEncUpdThreads);
-  }
-  __device__ __forceinline__ void store(uint4* lds) const {
-    enc_u32x4* l = reinterpret_cast<enc_u32x4*>(lds) + kFront / 16;
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kEncUpdThreads < blocks) l[threadIdx.x + k * kEncUpdThreads] = v[k];
-  }
-};
-
-// Four bytes of LDS from any byte address (two aligned dword reads + v_alignbyte).
-__device__ __forceinline__ uint32_t enc_lds_u32_at(const uint32_t* w, uint32_t at) {
-  return __builtin_amdgcn_alignbyte(w[(at >> 2) + 1], w[at >> 2], at & 3u);
-}
+// A tile's span (it may be empty), behind the front block.
+using EncStage = b64d::Stage<kPer, kEncUpdThreads, kFront / 16>;
 
 // What a piece writes, in 32 bits: the launch's clamps have made everything fit.
 struct EncPiece {
@@ -104,21 +76,6 @@ struct EncPiece {
   uint32_t rest;
   uint32_t lo, hi;   // the text positions written: [lo, hi), hi at most the cap
 };
-
-// The 16-byte block at text position pos, clipped to [lo, hi): one 16-byte store
-// when it lies wholly inside and is aligned, bytes otherwise.
-__device__ __forceinline__ void enc_put_block(uint8_t* text, uint32_t pos, uint32_t lo, uint32_t hi, uint4 v) {
-  uint8_t* dst = text + pos;
-  if (pos >= lo && pos + 16 <= hi && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-    const enc_u32x4 x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<enc_u32x4*>(dst));
-    return;
-  }
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t m = 0; m < 16; ++m)
-    if (pos + m >= lo && pos + m < hi) dst[m] = (uint8_t)(w[m >> 2] >> (8 * (m & 3)));
-}
 
 // One tile of the chunk's text from the staged bytes: chunk byte c is LDS byte
 // bias + c (mod 2^32).  Lane v writes characters [16v, 16v + 16) of the tile.
@@ -138,14 +95,9 @@ __device__ __forceinline__ void enc_tile(const uint32_t* w, uint32_t bias, const
   // group gg of the chunk as its four characters, first character in the low byte
   auto chars = [&](uint32_t gg) -> uint32_t {
     if (!kWhole && (gg < pc.g0 || gg >= pc.g1 + pc.partial)) return 0u;  // not this piece's
-    const uint32_t b = enc_lds_u32_at(w, bias + 3 * gg);
-    uint32_t x = __builtin_amdgcn_perm(0u, b, 0x0C000102u);  // the group's three bytes, big-endian
-    if (kWhole || gg < pc.g1)
-      return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 | (uint32_t)alpha[(x >> 6) & 63] << 16 |
-             (uint32_t)alpha[x & 63] << 24;
-    x &= pc.rest == 2 ? 0xFFFF00u : 0xFF0000u;  // the last one or two bytes: "xxx=" / "xx=="
-    return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 |
-           (pc.rest == 2 ? (uint32_t)alpha[(x >> 6) & 63] : (uint32_t)'=') << 16 | (uint32_t)'=' << 24;
+    const uint32_t x = b64d::group_bits(w, bias + 3 * gg);
+    if (kWhole || gg < pc.g1) return b64d::chars_whole(alpha, x);
+    return b64d::chars_last(alpha, x, pc.rest);
   };
   for (uint32_t v = threadIdx.x; v < kText / 16; v += kEncUpdThreads) {
     const uint32_t p0 = 16 * v, pos = tbeg + p0;
@@ -170,7 +122,7 @@ __device__ __forceinline__ void enc_tile(const uint32_t* w, uint32_t bias, const
       out = make_uint4(__builtin_amdgcn_alignbyte(E[1], E[0], sh), __builtin_amdgcn_alignbyte(E[2], E[1], sh),
                        __builtin_amdgcn_alignbyte(E[3], E[2], sh), __builtin_amdgcn_alignbyte(E[4], E[3], sh));
     }
-    enc_put_block(pc.text, pos, pc.lo, pc.hi, out);
+    b64d::put_block(pc.text, pos, pc.lo, pc.hi, out);
   }
 }
 
@@ -197,10 +149,7 @@ __global__ void __launch_bounds__(kEncUpdThreads) b64_encode_update_kernel(EncUp
   const uint32_t cap = p.cap[i];
   const bool fin = p.final_flags != nullptr && p.final_flags[i] != 0;
   const uint32_t layout = (r.w >> 8) & 1u;
-  if (threadIdx.x < 64) {
-    const uint32_t c = threadIdx.x;
-    alpha[c] = (uint8_t)(c < 26 ? 'A' + c : c < 52 ? 'a' + (c - 26) : c < 62 ? '0' + (c - 52) : c == 62 ? '+' : '/');
-  }
+  b64d::fill_alphabet(alpha);
   __syncthreads();
   if (cap > kEncMaxTextCap) {  // refused: nothing encoded, nothing for the hash (b64_encode_sizes_kernel), verdict 0
     if (threadIdx.x == 0) {
@@ -253,7 +202,9 @@ __global__ void __launch_bounds__(kEncUpdThreads) b64_encode_update_kernel(EncUp
       const uint32_t tb = tile * kEncUpdTileBytes, te = tb + kEncUpdTileBytes;
       cbeg = tb > t ? tb : t;
       const uint32_t cend = te < tend ? te : tend;
-      st.load(src + (cbeg - t), cend > cbeg ? cend - cbeg : 0u);
+      const uint32_t len = cend > cbeg ? cend - cbeg : 0u;
+      st.clear();
+      if (len != 0) st.load(src + (cbeg - t), len);
     };
     load(k0);  // k0's tile starts at or below 3 * g0 <= t: its span starts at the piece's first byte
     st.store(stage[0]);

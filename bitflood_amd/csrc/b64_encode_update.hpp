@@ -1,10 +1,11 @@
-// b64_encode_update.hpp -- the geometry of the resumable base64 encode
-// (lbf_b64_enc_state, lbf_hash.h): where a group's characters lie in a chunk's
-// text in either peer layout, how long the text is, and the tile the kernel of
-// b64_encode_update.hip lays over it.  Plain constexpr arithmetic, no HIP: the
-// kernel, the launch and the batch call's planner (b64_encode_plan.hpp) all
-// read the rule from here, and tests/test_b64_encode_cpu.py reads the constants
-// back.  DESIGN.md §4.8.
+// b64_encode_update.hpp -- the geometry of a chunk's base64 text, stated once
+// for every wire call: xmlrpc++'s line, where a group's characters lie in
+// either peer layout, how long the text is, and the wire calls' bound on a
+// chunk; and the tile the kernel of b64_encode_update.hip (the resumable
+// encode, lbf_b64_enc_state, lbf_hash.h) lays over it.  Plain constexpr
+// arithmetic, no HIP: the kernels, the launches and the batch calls' planners
+// all read the rule from here, and tests/test_b64_encode_cpu.py reads the
+// constants back.  DESIGN.md §4.8.
 #pragma once
 
 #include <stdint.h>
@@ -43,8 +44,9 @@ LBF_ENC_HD constexpr uint64_t text_length(uint64_t n, bool flat) {
   return group_pos(n / 3, flat) + (n % 3 ? 4 : 0);
 }
 
-// The wire calls' bound on a chunk, and the longest text such a chunk has: the
-// kernel keeps positions within a chunk's text in 32 bits.
+// The wire calls' bound on a chunk, encode and decode, one-shot and piecewise
+// (1 GiB), and the longest text such a chunk has: the kernels keep positions
+// within a chunk and its text in 32 bits.
 constexpr uint64_t kEncMaxChunk = 1ull << 30;
 constexpr uint64_t kEncMaxTextCap = text_length(kEncMaxChunk, false);  // 1,451,539,875
 static_assert(kEncMaxTextCap + kEncUpdTileText < (1ull << 32), "text positions fit 32 bits");

@@ -37,8 +37,8 @@
 //       restates the rule and tests/test_b64_flat_cpu.py holds it to the
 //       general one.
 //
-// A translation unit of its own: the other kernels' ISA stays as recorded.
-// The staging, the table entry, the packing and the piecewise stage itself
+// The staging, the table entry, the window and the packing are
+// b64_device.hpp's; the tile's geometry and the piecewise stage itself
 // (flat_stage) are b64_update_stages.hpp's, which the fused kernel
 // (b64_update_fused.hip) uses too.  DESIGN.md §4.7.
 #include <hip/hip_runtime.h>
@@ -48,6 +48,7 @@
 #include <algorithm>
 #include <atomic>
 
+#include "b64_device.hpp"
 #include "b64_flat.hpp"
 #include "b64_update_stages.hpp"
 #include "lbf_internal.hpp"

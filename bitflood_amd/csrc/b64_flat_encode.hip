@@ -30,12 +30,13 @@
 // byte outside text[text_off[i], + 4 * ceil(size[i] / 3)) is written, so slots
 // may touch at any phase.
 //
-// A translation unit of its own: sha1_kernels.hip's ISA stays as recorded
-// (tests/test_isa.py).  DESIGN.md §4.5.
+// The staging, the block store, the alphabet and a group's characters are
+// b64_device.hpp's, shared with the line kernel.  DESIGN.md §4.5.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
+#include "b64_device.hpp"
 #include "b64_flat_encode.hpp"
 #include "lbf_internal.hpp"
 
@@ -57,48 +58,10 @@ constexpr uint32_t kStageBlocks = kTileBytes / 16 + 3;
 static_assert(15 + 12 * (kTileBlocks - 1) + 16 <= 16 * kStageBlocks, "the window stays inside the stage");
 constexpr uint32_t kPer = (kTileBytes / 16 + 1 + kThreads - 1) / kThreads;  // staged blocks per lane
 // text positions within a chunk are 32-bit: the largest chunk's text and the tiles a grid may add behind it
-static_assert(4ull * ((uint64_t)kWireMaxChunk / 3 + 1) + (uint64_t)kTilesPerGroup * kTileText < (1ull << 32),
+static_assert(4ull * (b64e::kEncMaxChunk / 3 + 1) + (uint64_t)kTilesPerGroup * kTileText < (1ull << 32),
               "text positions fit 32 bits");
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-// Global bytes [src, src + len), len > 0, as the aligned 16-byte blocks that
-// hold them: afterwards LDS byte (delta + k) = src[k], delta = src mod 16.
-// load() issues the loads and returns; store() waits for them and writes LDS,
-// so the tile in hand encodes while the next one's bytes fly.
-struct Stage {
-  u32x4 v[kPer];
-  uint32_t blocks = 0, delta = 0;
-  __device__ __forceinline__ void load(const uint8_t* src, uint32_t len) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    delta = (uint32_t)(a & 15u);
-    const u32x4* g = reinterpret_cast<const u32x4*>(a - delta);
-    blocks = (delta + len + 15) / 16;  // at most kTileBytes / 16 + 1
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) v[k] = __builtin_nontemporal_load(g + threadIdx.x + k * kThreads);
-  }
-  __device__ __forceinline__ void store(uint4* lds) const {
-    u32x4* l = reinterpret_cast<u32x4*>(lds);
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) l[threadIdx.x + k * kThreads] = v[k];
-  }
-};
-
-// The 16-byte block v to t[pos, pos + 16), clipped to the slot's end: one
-// 16-byte store when it is whole and aligned, bytes otherwise.
-__device__ __forceinline__ void put_block(uint8_t* t, uint32_t pos, uint64_t end, uint4 v) {
-  uint8_t* dst = t + pos;
-  if ((uint64_t)pos + 16 <= end && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-    const u32x4 x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(dst));
-    return;
-  }
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t m = 0; m < 16; ++m)
-    if ((uint64_t)pos + m < end) dst[m] = (uint8_t)(w[m >> 2] >> (8 * (m & 3)));
-}
+using b64d::put_block;
+using Stage = b64d::Stage<kPer, kThreads, 0>;  // a tile's span, len > 0: at most kTileBytes / 16 + 1 blocks
 
 // One tile of the text from its bytes in LDS (w, from byte `delta`): block u of
 // the tile, characters [16u, 16u + 16), is groups 4u .. 4u + 3, the twelve
@@ -114,12 +77,7 @@ __device__ __forceinline__ void encode_tile(const uint32_t* w, uint32_t delta, c
   // group gg of the chunk, its three bytes in x, as its four characters, first character in the low byte
   auto chars = [&](uint32_t x, uint32_t gg) -> uint32_t {
     if (!kWhole && (gg > full || (gg == full && rest == 0))) return 0u;  // past the text: cut away by the slot's end
-    if (kWhole || gg < full)
-      return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 | (uint32_t)alpha[(x >> 6) & 63] << 16 |
-             (uint32_t)alpha[x & 63] << 24;
-    x &= rest == 2 ? 0xFFFF00u : 0xFF0000u;  // the last one or two bytes: "xxx=" / "xx=="
-    return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 |
-           (rest == 2 ? (uint32_t)alpha[(x >> 6) & 63] : (uint32_t)'=') << 16 | (uint32_t)'=' << 24;
+    return kWhole || gg < full ? b64d::chars_whole(alpha, x) : b64d::chars_last(alpha, x, rest);
   };
   for (uint32_t u = threadIdx.x; u < kTileBlocks; u += kThreads) {
     const uint32_t pos = tbeg + 16 * u;
@@ -134,7 +92,7 @@ __device__ __forceinline__ void encode_tile(const uint32_t* w, uint32_t delta, c
                                  chars(__builtin_amdgcn_perm(d1, d0, 0x0C030405u), g + 1),
                                  chars(__builtin_amdgcn_perm(d2, d1, 0x0C020304u), g + 2),
                                  chars(__builtin_amdgcn_perm(0u, d2, 0x0C010203u), g + 3));
-    put_block(t, pos, tl, out);
+    put_block(t, (uint64_t)pos, (uint64_t)0, tl, out);  // clipped to the slot's end
   }
 }
 
@@ -163,15 +121,11 @@ __global__ void __launch_bounds__(kThreads) b64_flat_encode_kernel(const uint8_t
   Stage st;
   auto load = [&](uint32_t tile) {
     const uint32_t dbeg = tile * kTileBytes;
-    st.blocks = 0;
-    st.delta = 0;
+    st.clear();
     if (dbeg < n) st.load(d + dbeg, min(kTileBytes, n - dbeg));  // below n: every tile below `own` starts there
   };
   load(t0);
-  if (threadIdx.x < 64) {
-    const uint32_t c = threadIdx.x;
-    alpha[c] = (uint8_t)(c < 26 ? 'A' + c : c < 52 ? 'a' + (c - 26) : c < 62 ? '0' + (c - 52) : c == 62 ? '+' : '/');
-  }
+  b64d::fill_alphabet(alpha);
   st.store(stage[0]);
   uint32_t delta = st.delta;
   __syncthreads();
@@ -202,7 +156,7 @@ __global__ void __launch_bounds__(256) b64_oversize_kernel(const uint32_t* __res
 int launch_b64_flat_encode(const uint8_t* data, const uint64_t* data_off, const uint32_t* size, uint8_t* text,
                            const uint64_t* text_off, uint32_t n, uint32_t max_size, hipStream_t stream) {
   if (n == 0) return LBF_OK;
-  if (max_size > kWireMaxChunk) return fail(LBF_ERR_INVALID, "flat encode: max_size over 1 GiB");
+  if (max_size > b64e::kEncMaxChunk) return fail(LBF_ERR_INVALID, "flat encode: max_size over 1 GiB");
   const uint64_t tl = 4 * (((uint64_t)max_size + 2) / 3);
   const uint32_t tiles = std::max<uint32_t>(1u, (uint32_t)((tl + kTileText - 1) / kTileText));
   constexpr uint32_t kPerLaunch = 65535;  // grid.y
@@ -224,9 +178,8 @@ extern "C" int lbf_verify_encode_b64_launch(const uint8_t* d_data, const uint64_
                                             const uint8_t* d_expected, uint8_t* d_verdicts, int layout, char* d_text,
                                             const uint64_t* d_text_offsets, void* stream) {
   const std::string who = "lbf_verify_encode_b64_launch";
-  if (layout != LBF_B64_LAYOUT_XMLRPC && layout != LBF_B64_LAYOUT_FLAT)
-    return fail(LBF_ERR_INVALID, who + ": layout is neither LBF_B64_LAYOUT_XMLRPC nor LBF_B64_LAYOUT_FLAT");
-  if (max_size > lbf::kWireMaxChunk)
+  if (int rc = lbf::check_b64_layout(who, layout)) return rc;
+  if (max_size > lbf::b64e::kEncMaxChunk)
     return fail(LBF_ERR_INVALID, who + ": max_size larger than the wire encode takes (1 GiB)");
   if (n == 0) return LBF_OK;
   if (!d_data || !d_offsets || !d_sizes || !d_text || !d_text_offsets)
@@ -249,14 +202,9 @@ extern "C" int lbf_verify_encode_b64_launch(const uint8_t* d_data, const uint64_
   // the hash with the usual selection (few chains run pc4), then the layout's encode from the same bytes
   if (d_digests || d_verdicts)
     if (int rc = lbf_sha1_launch(d_data, d_offsets, d_sizes, n, d_digests, d_expected, d_verdicts, st)) return rc;
-  if (layout == LBF_B64_LAYOUT_FLAT) {
-    if (int rc =
-            lbf::launch_b64_flat_encode(d_data, d_offsets, d_sizes, text, d_text_offsets, (uint32_t)n, max_size, st))
-      return rc;
-  } else {
-    if (int rc = lbf::launch_b64_encode(d_data, d_offsets, d_sizes, text, d_text_offsets, (uint32_t)n, max_size, st))
-      return rc;
-  }
+  if (int rc = lbf::launch_b64_encode_for(layout, d_data, d_offsets, d_sizes, text, d_text_offsets, (uint32_t)n, max_size,
+                                          st))
+    return rc;
   if (d_verdicts) {  // behind the hash on the stream: the verdict of a chunk whose text is incomplete does not stand
     hipLaunchKernelGGL(lbf::b64_oversize_kernel, dim3(((uint32_t)n + 255u) / 256u), dim3(256), 0, st, d_sizes, max_size,
                        d_verdicts, (uint32_t)n);

@@ -20,12 +20,11 @@
 #include <utility>
 #include <vector>
 
+#include "b64_encode_update.hpp"
 #include "lbf_hash.h"
 #include "update_plan.hpp"
 
 namespace lbf {
-
-constexpr uint64_t kB64MaxChunk = 1ull << 30;  // the wire calls' bound on a chunk
 
 // The bytes a state with `ncarry` pending sextets can gain from `len`
 // characters: every complete group three, and a closing "xx=" / "xxx=" at most
@@ -59,7 +58,7 @@ inline bool b64_piece_ok(const lbf_b64_state* b64, const lbf_sha1_state* sha, ui
     why = "has text outside [text, text+text_len)";
     return false;
   }
-  if (cap > kB64MaxChunk) {
+  if (cap > b64e::kEncMaxChunk) {
     why = "is of a chunk of " + std::to_string(cap) + " bytes, more than 1 GiB";
     return false;
   }

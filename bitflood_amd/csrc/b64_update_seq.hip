@@ -54,6 +54,8 @@ __device__ __forceinline__ SeqLane seq_lane() {
 }
 }  // namespace b64s
 }  // namespace lbf
+// b64_device.hpp's helpers (the staging, the scan) read the lane number too: that header is first included from
+// the stages header, inside the definition below, and nothing above may include it.
 #define threadIdx (::lbf::b64s::seq_lane())
 #include "b64_update_stages.hpp"
 #undef threadIdx

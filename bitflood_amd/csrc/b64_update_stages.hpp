@@ -17,15 +17,19 @@
 // record, the piece's length and what a stage took are the same in every lane,
 // and no function here leaves early in some lanes only.  DESIGN.md §4.7.
 //
-// What the stages need of kern_b64.hpp (the staging, the table entry, the
-// block) is restated here: that header belongs to sha1_kernels.hip's
-// translation unit, whose ISA stays as recorded.
+// The staging, the table entry, the block store, the packing, the window of
+// unbroken text and the scan's prefix sum are b64_device.hpp's, shared with the
+// one-shot kernels.  The window of a tile of lines (decode_line_block) is
+// kern_b64.hpp's b64_decode_block written out again: as a shared function it
+// changes the recorded ISA of b64_update_seq_kernel and of the one-pass decode.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "b64_device.hpp"
+#include "b64_encode_update.hpp"
 #include "lbf_hash.h"
 
 namespace lbf {
@@ -33,12 +37,11 @@ namespace b64s {
 
 constexpr uint32_t kThreads = 256;
 constexpr uint32_t kWaves = kThreads / 64;
-constexpr uint32_t kMaxCap = 1u << 30;  // the wire calls' bound on a chunk
+constexpr uint32_t kMaxCap = (uint32_t)b64e::kEncMaxChunk;  // the wire calls' bound on a chunk
 // A chain's byte count stays at or below this (the host call refuses a record at
 // or past it).  read_rec clamps what it loads to it and a piece adds less than
 // 2^32, so no position ever wraps, whatever a forged record claims.
 constexpr uint64_t kMaxDecoded = 1ull << 61;
-constexpr uint32_t kEq = 64, kSkip = 255;
 // Tiles are laid over the CHUNK: block u of tile k holds chunk bytes [3888k +
 // 16u, +16), from 72 lines (5,256 characters) or 5,184 unbroken characters.
 constexpr uint32_t kTileBytes = 3888, kTileGroups = kTileBytes / 3, kTileBlocks = kTileBytes / 16;  // 1,296 / 243
@@ -56,17 +59,24 @@ constexpr uint32_t kSx = kTrip + 16;       // 4,096 + 3 sextets, whole 16-byte b
 // The tile stages' two buffers and the scan's sextets are never live together.
 constexpr uint32_t kStageBytes = 2 * kStage * 16;
 static_assert(kSx <= kStageBytes, "the scan's sextets fit the tile buffers");
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 static_assert(sizeof(lbf_b64_state) == 16 && offsetof(lbf_b64_state, decoded) == 0 &&
                   offsetof(lbf_b64_state, carry) == 8 && offsetof(lbf_b64_state, ncarry) == 12 &&
                   offsetof(lbf_b64_state, ended) == 13 && offsetof(lbf_b64_state, zero) == 14,
               "lbf_b64_state layout");
 
-// The decode table entry of character c: 0..63, kEq for '=', kSkip otherwise.
-__device__ __forceinline__ uint32_t value(uint32_t c) {
-  return c - 'A' < 26u ? c - 'A' : c - 'a' < 26u ? c - 'a' + 26 : c - '0' < 10u ? c - '0' + 52 :
-         c == '+' ? 62u : c == '/' ? 63u : c == '=' ? kEq : kSkip;
+using b64d::kEq;
+using b64d::kSkip;
+using b64d::pack16;
+using b64d::six_groups;
+using b64d::value;
+// A tile's text staged behind kPad blocks (b64_device.hpp): LDS byte 16 * kPad + (src mod 16) + k = src[k].  The
+// tile in hand decodes while the next one's text flies.
+using Stage = b64d::Stage<kPer, kThreads, kPad>;
+
+// Bytes [lo, hi) of the 16-byte block v to o[lo .. hi), with a plain store: the hash reads these bytes next.
+__device__ __forceinline__ void put_block(uint8_t* o, uint4 v, uint32_t lo, uint32_t hi) {
+  b64d::put_block<false>(o, 0u, lo, hi, v);
 }
 
 // A chain's record in registers, clamped: whatever a forged record says, the
@@ -101,56 +111,6 @@ struct Piece {
   uint32_t cap;
 };
 
-// Global bytes [src, src + len) into LDS as the aligned 16-byte blocks that
-// hold them (a block that holds one byte of the span lies in its page): LDS
-// byte 16 * kPad + (src mod 16) + k = src[k].  load() issues the loads, store()
-// waits for them, so the tile in hand decodes while the next one's text flies.
-struct Stage {
-  u32x4 v[kPer];
-  uint32_t blocks = 0;
-  __device__ __forceinline__ void load(const uint8_t* src, uint32_t len) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    const uint32_t phase = (uint32_t)(a & 15u);
-    const u32x4* g = reinterpret_cast<const u32x4*>(a - phase);
-    blocks = (phase + len + 15) / 16;  // at most kSpan
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) v[k] = __builtin_nontemporal_load(g + threadIdx.x + k * kThreads);
-  }
-  __device__ __forceinline__ void store(uint4* lds) const {
-    u32x4* l = reinterpret_cast<u32x4*>(lds) + kPad;
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kThreads < blocks) l[threadIdx.x + k * kThreads] = v[k];
-  }
-};
-
-// Bytes [phase, phase + 16) of six groups' 18: group j's bytes are x[j]'s
-// bytes 2, 1, 0, one v_perm_b32 per little-endian word (selector bytes 0-3
-// pick from the second source, 4-7 from the first, 12 gives 0).
-__device__ __forceinline__ uint4 pack16(const uint32_t x[6], uint32_t phase) {
-  const uint32_t W0 = __builtin_amdgcn_perm(x[1], x[0], 0x06000102u);
-  const uint32_t W1 = __builtin_amdgcn_perm(x[2], x[1], 0x05060001u);
-  const uint32_t W2 = __builtin_amdgcn_perm(x[3], x[2], 0x04050600u);
-  const uint32_t W3 = __builtin_amdgcn_perm(x[5], x[4], 0x06000102u);
-  const uint32_t W4 = __builtin_amdgcn_perm(x[5], x[5], 0x0C0C0001u);
-  return make_uint4(__builtin_amdgcn_alignbyte(W1, W0, phase), __builtin_amdgcn_alignbyte(W2, W1, phase),
-                    __builtin_amdgcn_alignbyte(W3, W2, phase), __builtin_amdgcn_alignbyte(W4, W3, phase));
-}
-
-// Bytes [lo, hi) of the 16-byte block v to o[lo .. hi): one 16-byte store when
-// that is all of it and o is aligned, bytes otherwise.  Nothing outside is written.
-__device__ __forceinline__ void put_block(uint8_t* o, uint4 v, uint32_t lo, uint32_t hi) {
-  if (lo == 0 && hi >= 16 && (reinterpret_cast<uintptr_t>(o) & 15u) == 0) {
-    *reinterpret_cast<uint4*>(o) = v;
-    return;
-  }
-  const uint32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t m = 0; m < 16; ++m)
-    if (m >= lo && m < hi) o[m] = (uint8_t)(ws[m >> 2] >> (8 * (m & 3)));
-}
-
 // The lane's block of a tile of lines: bytes [16 * lane, +16) of the tile from
 // its six groups g0 .. g0 + 5 (kern_b64.hpp's b64_decode_block), of which only
 // groups [gl, gh) of the tile are this piece's.  Character c of the tile is LDS
@@ -160,9 +120,9 @@ __device__ __forceinline__ void put_block(uint8_t* o, uint4 v, uint32_t lo, uint
 // [gl, gh) are whatever lay in LDS; the caller stores none of them.
 __device__ __forceinline__ uint4 decode_line_block(const uint8_t* sb, uint32_t delta, const uint8_t* tab, uint32_t gl,
                                                    uint32_t gh, uint32_t sep_hi, bool* bad) {
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(sb);
   const uint32_t b0 = 16 * threadIdx.x, g0 = b0 / 3, phase = b0 - 3 * g0;
   const uint32_t l0 = g0 / 18, r0 = g0 - 18 * l0;
+  const uint32_t* w = reinterpret_cast<const uint32_t*>(sb);
   const uint32_t c0 = delta + 4 * g0 + l0, sh0 = c0 & 3u;
   const uint32_t* wb = w + (c0 >> 2);
   uint32_t win[8];
@@ -189,34 +149,6 @@ __device__ __forceinline__ uint4 decode_line_block(const uint8_t* sb, uint32_t d
   }
   *bad = b;
   return pack16(x, phase);
-}
-
-// The lane's six groups of a tile of unbroken text, g0 = 16 * lane / 3
-// onwards, from LDS bytes [c0, c0 + 24): one window of seven aligned dwords,
-// each group cut out of it with v_alignbyte.  x[j] = group j's 24 bits, joined
-// unmasked (a flagged group's bytes are never stored as data).  Table entries
-// are 0..63, '=' 64 and anything else 255, so (entry >> 6) is 0 exactly for an
-// alphabet character: two flag bits per group at 2j, for all four characters
-// (*inner) and for the first two (*head).
-__device__ __forceinline__ void six_groups(const uint8_t* sb, uint32_t c0, const uint8_t* tab, uint32_t x[6],
-                                           uint32_t* inner, uint32_t* head) {
-  const uint32_t* wb = reinterpret_cast<const uint32_t*>(sb) + (c0 >> 2);
-  const uint32_t sh = c0 & 3u;  // the same in every lane: a group is four characters
-  uint32_t win[7];
-#pragma unroll
-  for (int k = 0; k < 7; ++k) win[k] = wb[k];
-  uint32_t fi = 0, fh = 0;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const uint32_t c = __builtin_amdgcn_alignbyte(win[j + 1], win[j], sh);
-    const uint32_t s0 = tab[c & 255], s1 = tab[(c >> 8) & 255], s2 = tab[(c >> 16) & 255], s3 = tab[c >> 24];
-    const uint32_t o2 = s0 | s1;
-    fi |= ((o2 | s2 | s3) >> 6) << (2 * j);
-    fh |= (o2 >> 6) << (2 * j);
-    x[j] = (((s0 << 6) | s1) << 12) | ((s2 << 6) | s3);
-  }
-  *inner = fi;
-  *head = fh;
 }
 
 // The head of both tile stages: a carried group is completed from the piece's
@@ -464,30 +396,6 @@ __device__ __forceinline__ uint32_t flat_stage(Rec& r, const Piece& pc, uint4 (*
   return pos + 4 * done;
 }
 
-// Exclusive scan of one value per lane over the workgroup (wg_exclusive_scan's
-// shape, kern_b64.hpp); `sums` is 4 words of LDS.
-__device__ __forceinline__ uint32_t scan256(uint32_t v, uint32_t* sums, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) sums[wave] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < (int)kWaves; ++w) {
-    const uint32_t s = sums[w];
-    before += w < wave ? s : 0u;
-    all += s;
-  }
-  __syncthreads();  // sums is reused by the next trip
-  *total = all;
-  return before + x - v;
-}
-
 // ---------------------------------------------------------------------------
 // The general scan (b64_update.hip has the rule): the text given as arbitrary
 // text, all of it, in trips of 4,096 characters.  The sextets of a trip go
@@ -543,7 +451,7 @@ __device__ __forceinline__ void scan_stage(Rec& r, const Piece& pc, uint8_t* sx,
       cnt += c[k] != kSkip;
     }
     uint32_t total;
-    uint32_t pos = nc + scan256(cnt, sums, &total);
+    uint32_t pos = nc + b64d::wg_exclusive_scan<kThreads>(cnt, sums, &total);
     // 4. sextets behind the carry; 5. the first '='.  pos < nc + 4,096 <= 4,099
 #pragma unroll
     for (int k = 0; k < 16; ++k) {

@@ -30,17 +30,22 @@
 // each for the text read and the sextets written and read back, 1 for the
 // bytes written).
 //
+// The helpers both directions share with the other base64 kernels (staging,
+// block store, table entry, alphabet, scan, packing) are b64_device.hpp's.
 // Part of the single translation unit sha1_kernels.hip (included from there).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include "b64_device.hpp"
+#include "b64_encode_update.hpp"
 #include "lbf_internal.hpp"
 
 namespace lbf {
 namespace {
 
-constexpr uint8_t kB64Eq = 64, kB64Skip = 255;
+using b64d::kEq;
+using b64d::kSkip;
 constexpr int kB64Threads = 256;  // one lane per entry of the decode table below
 
 struct B64Table {
@@ -49,41 +54,17 @@ struct B64Table {
 
 constexpr B64Table make_b64_table() {
   B64Table t{};
-  for (int c = 0; c < 256; ++c) t.v[c] = kB64Skip;
+  for (int c = 0; c < 256; ++c) t.v[c] = (uint8_t)kSkip;
   for (int c = 'A'; c <= 'Z'; ++c) t.v[c] = (uint8_t)(c - 'A');
   for (int c = 'a'; c <= 'z'; ++c) t.v[c] = (uint8_t)(26 + c - 'a');
   for (int c = '0'; c <= '9'; ++c) t.v[c] = (uint8_t)(52 + c - '0');
   t.v['+'] = 62;
   t.v['/'] = 63;
-  t.v['='] = kB64Eq;
+  t.v['='] = (uint8_t)kEq;
   return t;
 }
 
 __constant__ B64Table g_b64_table = make_b64_table();
-
-// Exclusive scan of one value per lane over the 256-lane workgroup; returns
-// the lane's prefix and writes the total to *total.  `sums` is 4 words of LDS.
-__device__ __forceinline__ uint32_t wg_exclusive_scan(uint32_t v, uint32_t* sums, uint32_t* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint32_t x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const uint32_t y = (uint32_t)__shfl_up((int)x, off, 64);
-    if (lane >= off) x += y;
-  }
-  if (lane == 63) sums[wave] = x;
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kB64Threads / 64; ++w) {
-    const uint32_t s = sums[w];
-    before += w < wave ? s : 0u;
-    all += s;
-  }
-  __syncthreads();  // sums is reused by the next call
-  *total = all;
-  return before + x - v;
-}
 
 // ---------------------------------------------------------------------------
 // Tiles of whole lines.  The encoder's text is lines of 18 groups: 72 alphabet
@@ -133,59 +114,15 @@ static_assert(kB64TileText % 16 == 0 && kB64TileBytes % 16 == 0, "tiles of 16-by
 constexpr uint32_t kDecLines = LBF_B64_DEC_LINES;
 constexpr uint32_t kDecText = kDecLines * 73, kDecBytes = kDecLines * 54, kDecGroups = kDecLines * 18;
 static_assert(kDecBytes % 16 == 0, "a decode tile is whole 16-byte blocks of output");
-typedef uint32_t b64_u32x4 __attribute__((ext_vector_type(4)));  // what the nontemporal builtins take
 
-// Stage global bytes [src, src + len) in LDS as the aligned 16-byte blocks that
-// hold them: afterwards lds byte (delta + k) = src[k], delta = src mod 16.  The
-// blocks are read whole (a 16-byte block holding one byte of the span lies in
-// the same page, so this never reads an unmapped address).  Up to kPer blocks
-// per lane.  load() issues all of a lane's loads and returns at once; store()
-// waits for them and writes LDS, so work placed between the two (the decode
-// table, the last group's check) runs while the loads are in flight.
+// A tile's span staged through registers into LDS (b64_device.hpp): LDS byte (delta + k) = src[k].
 template <uint32_t kPer>
-struct B64Stage {
-  b64_u32x4 v[kPer];
-  uint32_t blocks = 0, delta = 0;
-  __device__ __forceinline__ void load(const uint8_t* src, uint32_t len) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(src);
-    delta = (uint32_t)(a & 15u);
-    const b64_u32x4* g = reinterpret_cast<const b64_u32x4*>(a - delta);
-    blocks = (delta + len + 15) / 16;
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kB64Threads < blocks) v[k] = __builtin_nontemporal_load(g + threadIdx.x + k * kB64Threads);
-  }
-  __device__ __forceinline__ void store(uint4* lds) const {
-    b64_u32x4* l = reinterpret_cast<b64_u32x4*>(lds);
-#pragma unroll
-    for (uint32_t k = 0; k < kPer; ++k)
-      if (threadIdx.x + k * kB64Threads < blocks) l[threadIdx.x + k * kB64Threads] = v[k];
-  }
-};
+using B64Stage = b64d::Stage<kPer, kB64Threads, 0>;
 
-// The decode table entry of character c (B64Table), computed: filling the LDS
-// copy this way costs a few VALU per lane and no dependent global load.
-__device__ __forceinline__ uint32_t b64_value(uint32_t c) {
-  return c - 'A' < 26u ? c - 'A' : c - 'a' < 26u ? c - 'a' + 26 : c - '0' < 10u ? c - '0' + 52 :
-         c == '+' ? 62u : c == '/' ? 63u : c == '=' ? (uint32_t)kB64Eq : (uint32_t)kB64Skip;
-}
-
-// Four bytes of LDS from any byte address (two aligned dword reads + v_alignbyte).
-__device__ __forceinline__ uint32_t lds_u32_at(const uint32_t* w, uint32_t at) {
-  return __builtin_amdgcn_alignbyte(w[(at >> 2) + 1], w[at >> 2], at & 3u);
-}
-
-// Store a 16-byte block to dst = base + pos, clipped to [0, end) of the slot:
-// one 16-byte store when it is whole and aligned, bytes otherwise.
+// Store a 16-byte block to base + pos, clipped to [0, end) of the slot: 64-bit
+// positions, and the byte tail as the loop that stops at the slot's end.
 __device__ __forceinline__ void b64_put_block(uint8_t* base, uint64_t pos, uint64_t end, uint4 v) {
-  uint8_t* dst = base + pos;
-  if (pos + 16 <= end && (reinterpret_cast<uintptr_t>(dst) & 15u) == 0) {
-    const b64_u32x4 x = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(x, reinterpret_cast<b64_u32x4*>(dst));
-    return;
-  }
-  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-  for (uint32_t m = 0; m < 16 && pos + m < end; ++m) dst[m] = (uint8_t)(w[m >> 2] >> (8 * (m & 3)));
+  b64d::put_block<true, true>(base, pos, (uint64_t)0, end, v);
 }
 
 // ---------------------------------------------------------------------------
@@ -302,18 +239,9 @@ __device__ __forceinline__ bool b64_decode_block(const uint8_t* sb, uint32_t del
     const uint32_t gs = gbase + js;
     const uint32_t at = (c0 & ~3u) + min(sh0 + 4 * js + 4, 31u);
     const bool check = r0 >= 12 && 4 * gs + gs / 18 + 4 < len;
-    bad |= check && tab[sb[at]] != kB64Skip;
+    bad |= check && tab[sb[at]] != kSkip;
   }
-  // the 18 bytes of the six groups, as little-endian words
-  // group j's bytes are x[j]'s bytes 2, 1, 0: one v_perm_b32 per word (selector
-  // bytes 0-3 pick from the second source, 4-7 from the first, 12 gives 0)
-  const uint32_t W0 = __builtin_amdgcn_perm(x[1], x[0], 0x06000102u);
-  const uint32_t W1 = __builtin_amdgcn_perm(x[2], x[1], 0x05060001u);
-  const uint32_t W2 = __builtin_amdgcn_perm(x[3], x[2], 0x04050600u);
-  const uint32_t W3 = __builtin_amdgcn_perm(x[5], x[4], 0x06000102u);
-  const uint32_t W4 = __builtin_amdgcn_perm(x[5], x[5], 0x0C0C0001u);
-  uint4 v = make_uint4(__builtin_amdgcn_alignbyte(W1, W0, phase), __builtin_amdgcn_alignbyte(W2, W1, phase),
-                       __builtin_amdgcn_alignbyte(W3, W2, phase), __builtin_amdgcn_alignbyte(W4, W3, phase));
+  uint4 v = b64d::pack16(x, phase);  // the 18 bytes of the six groups, cut to the block's 16
   const uint64_t pos = (uint64_t)tile * kDecBytes + b0;
   if (pos < limit) {
     if (pos + 16 > want) {  // the decoded bytes end inside this block: zero the rest of the slot
@@ -394,21 +322,20 @@ __global__ void __launch_bounds__(kB64Threads) b64_decode_canon_kernel(const uin
   B64Stage<kPer> st;
   auto load = [&](uint32_t tile) {
     const uint32_t tbeg = tile * kDecText;
-    st.blocks = 0;
-    st.delta = 0;
+    st.clear();
     if (tbeg < len) st.load(t + tbeg, min(kDecText, len - tbeg));
   };
   load(t0);
-  tab[threadIdx.x] = (uint8_t)b64_value(threadIdx.x);
+  tab[threadIdx.x] = (uint8_t)b64d::value(threadIdx.x);
   if (threadIdx.x == 0) {
     // the last group -- "xxxx", "xxx=" or "xx==" -- sets the decoded length
     uint32_t last = 3;
     bool bad = false;
     if (groups > 0) {
       const uint32_t g = groups - 1, at = 4 * g + g / 18;
-      const uint32_t c2 = b64_value(t[at + 2]), c3 = b64_value(t[at + 3]);
+      const uint32_t c2 = b64d::value(t[at + 2]), c3 = b64d::value(t[at + 3]);
       last = c3 < 64 ? 3u : c2 < 64 ? 2u : 1u;
-      bad = c3 == kB64Skip || c2 == kB64Skip || (c2 == kB64Eq && c3 != kB64Eq);
+      bad = c3 == kSkip || c2 == kSkip || (c2 == kEq && c3 != kEq);
     }
     last_shared = last;
     if (t0 == 0) {
@@ -496,14 +423,14 @@ __global__ void __launch_bounds__(kB64Threads) b64_decode_kernel(const uint8_t* 
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
       c[k] = tab[c[k]];
-      cnt += c[k] != kB64Skip;
+      cnt += c[k] != kSkip;
     }
     uint32_t total;
-    uint32_t pos = base + wg_exclusive_scan(cnt, sums, &total);
+    uint32_t pos = base + b64d::wg_exclusive_scan<kB64Threads>(cnt, sums, &total);
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      if (c[k] == kB64Skip) continue;
-      if (c[k] == kB64Eq) atomicMin(&first_eq, pos);
+      if (c[k] == kSkip) continue;
+      if (c[k] == kEq) atomicMin(&first_eq, pos);
       s[pos++] = c[k];
     }
     base += total;
@@ -584,9 +511,15 @@ namespace {
 // independently.  blockIdx.x = chunk; data[data_off[i] .. + size[i]) ->
 // text[text_off[i] .. + b64_put_length(size[i])).
 // ---------------------------------------------------------------------------
+// b64e::text_length(size, false), summed in the order the recorded kernel has
+// it: called from here the shared form adds an instruction to b64_encode_kernel.
 __host__ __device__ constexpr uint64_t b64_put_length(uint64_t size) {
   return 4 * (size / 3) + (size % 3 ? 4 : 0) + size / 3 / 18;
 }
+static_assert(b64_put_length(1) == b64e::text_length(1, false) && b64_put_length(54) == b64e::text_length(54, false) &&
+                  b64_put_length(3457) == b64e::text_length(3457, false) &&
+                  b64_put_length(b64e::kEncMaxChunk) == b64e::kEncMaxTextCap,
+              "one text length");
 
 // One tile of the encode from its bytes in LDS (sb, from byte `delta`): lane
 // v writes characters [16v, 16v + 16) of the tile's text.  Characters [p, p +
@@ -610,14 +543,9 @@ __device__ __forceinline__ void b64_encode_tile(const uint8_t* sb, uint32_t delt
   auto chars = [&](uint32_t gl) -> uint32_t {
     const uint32_t gg = tile * kB64TileGroups + gl;
     if (!kWhole && (gg > full || (gg == full && rest == 0))) return 0u;  // past the text
-    const uint32_t b = lds_u32_at(w, delta + 3 * gl);
-    uint32_t x = __builtin_amdgcn_perm(0u, b, 0x0C000102u);  // the group's three bytes, big-endian
-    if (kWhole || gg < full)
-      return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 | (uint32_t)alpha[(x >> 6) & 63] << 16 |
-             (uint32_t)alpha[x & 63] << 24;
-    x &= rest == 2 ? 0xFFFF00u : 0xFF0000u;  // the last one or two bytes: "xxx=" / "xx=="
-    return (uint32_t)alpha[x >> 18] | (uint32_t)alpha[(x >> 12) & 63] << 8 |
-           (rest == 2 ? (uint32_t)alpha[(x >> 6) & 63] : (uint32_t)'=') << 16 | (uint32_t)'=' << 24;
+    const uint32_t x = b64d::group_bits(w, delta + 3 * gl);
+    if (kWhole || gg < full) return b64d::chars_whole(alpha, x);
+    return b64d::chars_last(alpha, x, rest);
   };
   for (uint32_t v = threadIdx.x; v < kB64TileText / 16; v += kB64Threads) {
     const uint32_t p0 = 16 * v;
@@ -666,15 +594,11 @@ __global__ void __launch_bounds__(kB64Threads) b64_encode_kernel(const uint8_t* 
   B64Stage<kPer> st;
   auto load = [&](uint32_t tile) {
     const uint32_t dbeg = tile * kB64TileBytes;
-    st.blocks = 0;
-    st.delta = 0;
+    st.clear();
     if (dbeg < n) st.load(d + dbeg, min(kB64TileBytes, n - dbeg));
   };
   load(t0);
-  if (threadIdx.x < 64) {
-    const uint32_t c = threadIdx.x;
-    alpha[c] = (uint8_t)(c < 26 ? 'A' + c : c < 52 ? 'a' + (c - 26) : c < 62 ? '0' + (c - 52) : c == 62 ? '+' : '/');
-  }
+  b64d::fill_alphabet(alpha);
   st.store(stage[0]);
   uint32_t delta = st.delta;
   __syncthreads();

@@ -28,19 +28,17 @@ int checked_slot_runs(const uint64_t* off, const uint64_t* len, uint64_t n, cons
   return fail(LBF_ERR_INVALID, std::string(who) + ": slot " + std::to_string(bad) + " overlaps another slot");
 }
 
-uint64_t up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
-
 // The wire kernels keep text and byte positions inside a chunk, and their
 // tile counts, in 32 bits (kern_b64.hpp): (len + tile - 1) / tile and
 // tile * tile_text must not wrap, so chunks are bounded well below 2^32.  The
 // reference's chunks are 64 KiB to a few MiB (Encoder.cpp:17-102); 1 GiB of
 // bytes encodes to 1.43 GB of text.  ADVICE r05: past 2^32 the positions
 // wrapped and tiles were never launched.
-constexpr uint64_t kB64MaxChunk = 1ull << 30, kB64MaxText = 3ull << 29;
+constexpr uint64_t kB64MaxText = 3ull << 29;
 
 }  // namespace
 
-extern "C" uint64_t lbf_b64_put_length(uint64_t size) { return 4 * (size / 3) + (size % 3 ? 4 : 0) + size / 3 / 18; }
+extern "C" uint64_t lbf_b64_put_length(uint64_t size) { return b64e::text_length(size, false); }
 
 namespace {
 
@@ -54,8 +52,7 @@ namespace {
 int verify_encode_b64(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, const uint64_t* offsets,
                       const uint32_t* sizes, uint64_t n, const uint8_t* expected, uint8_t* verdicts, int layout,
                       char* text, uint64_t text_len, const uint64_t* text_offsets, const std::string& who) {
-  if (layout != LBF_B64_LAYOUT_XMLRPC && layout != LBF_B64_LAYOUT_FLAT)
-    return fail(LBF_ERR_INVALID, who + ": layout is neither LBF_B64_LAYOUT_XMLRPC nor LBF_B64_LAYOUT_FLAT");
+  if (int rc = check_b64_layout(who, layout)) return rc;
   if (n != 0 && (!data || !offsets || !sizes || !expected || !verdicts || !text || !text_offsets))
     return fail(LBF_ERR_INVALID, who + ": null argument");
   if (!ctx) return fail(LBF_ERR_INVALID, "null context");
@@ -65,7 +62,7 @@ int verify_encode_b64(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, cons
   std::vector<uint64_t> tlens(n);
   uint32_t max_size = 0;
   for (uint64_t i = 0; i < n; ++i) {
-    if (sizes[i] > kB64MaxChunk)
+    if (sizes[i] > b64e::kEncMaxChunk)
       return fail(LBF_ERR_INVALID, who + ": chunk " + std::to_string(i) + " larger than the wire encode takes (1 GiB)");
     if (offsets[i] > data_len || sizes[i] > data_len - offsets[i])
       return fail(LBF_ERR_INVALID, who + ": chunk " + std::to_string(i) + " outside the buffer");
@@ -94,8 +91,9 @@ int verify_encode_b64(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, cons
     }
     memcpy(sz + n, expected, 20 * n);
     // device layout: bytes | text | inputs (offsets, text offsets, sizes, expected) | verdicts
-    const uint64_t data_b = up(dhi - dlo + 16, 256), text_b = up(thi - tlo + 16, 256), in_b = up(in.size(), 256);
-    const uint64_t need = data_b + text_b + in_b + up(n, 256);
+    const uint64_t data_b = round_up(dhi - dlo + 16, 256), text_b = round_up(thi - tlo + 16, 256);
+    const uint64_t in_b = round_up(in.size(), 256);
+    const uint64_t need = data_b + text_b + in_b + round_up(n, 256);
     std::lock_guard<std::mutex> lock(ctx->mu);
     KeepCurrentDevice keep;
     Worker& w = ctx->workers[0];
@@ -114,9 +112,7 @@ int verify_encode_b64(lbf_ctx* ctx, const uint8_t* data, uint64_t data_len, cons
     const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_toff + n);
     const uint8_t* d_exp = reinterpret_cast<const uint8_t*>(d_sz + n);
     if (int rc = lbf_sha1_launch(d_data, d_doff, d_sz, n, nullptr, d_exp, d_ver, st)) return rc;
-    if (int rc = layout == LBF_B64_LAYOUT_FLAT
-                     ? lbf::launch_b64_flat_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st)
-                     : lbf::launch_b64_encode(d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st))
+    if (int rc = launch_b64_encode_for(layout, d_data, d_doff, d_sz, d_text, d_toff, (uint32_t)n, max_size, st))
       return rc;
     LBF_HIP_TRY(hipMemcpyAsync(verdicts, d_ver, n, hipMemcpyDeviceToHost, st));
     for (const SlotRun& r : runs)
@@ -177,7 +173,7 @@ struct B64Verify {
 int b64_verify_check(B64Verify& v, uint64_t text_len, uint64_t out_len) {
   const uint64_t n = v.n;
   for (uint64_t i = 0; i < n; ++i) {
-    if (v.text_lens[i] > kB64MaxText || v.expected_sizes[i] > kB64MaxChunk)
+    if (v.text_lens[i] > kB64MaxText || v.expected_sizes[i] > b64e::kEncMaxChunk)
       return fail(LBF_ERR_INVALID, "lbf_b64_verify_batch: chunk " + std::to_string(i) +
                                        " larger than the wire decode takes (1 GiB of bytes, 1.5 GiB of text)");
     if (v.text_offsets[i] > text_len || v.text_lens[i] > text_len - v.text_offsets[i])
@@ -230,7 +226,7 @@ std::vector<uint8_t> b64_verify_tables(const B64Verify& v, uint64_t& sext, uint6
     const uint64_t i = v.order[k];
     toff[k] = v.text_offsets[i] - v.tlo;
     soff[k] = sext;
-    sext += up(v.text_lens[i], 16);
+    sext += round_up(v.text_lens[i], 16);
     tlen[k] = v.text_lens[i];
     cap[k] = v.expected_sizes[i];
     memcpy(exp.data() + 20 * k, v.expected + 20 * i, 20);
@@ -238,7 +234,7 @@ std::vector<uint8_t> b64_verify_tables(const B64Verify& v, uint64_t& sext, uint6
       ooff[k] = v.out_offsets[i] - v.olo;
     } else {
       ooff[k] = outb;
-      outb += up(v.expected_sizes[i], 16);
+      outb += round_up(v.expected_sizes[i], 16);
     }
   }
   if (v.out) outb = v.ohi - v.olo;
@@ -288,8 +284,8 @@ int b64_verify_run(lbf_ctx* ctx, const B64Verify& v) {
   uint64_t sext = 0, outb = 0;
   const std::vector<uint8_t> in = b64_verify_tables(v, sext, outb);
   // device layout: text | sextets | bytes | inputs then, right behind them, the results
-  const uint64_t text_b = up(v.thi - v.tlo, 256), sext_b = up(sext, 256), out_b = up(outb + 16, 256);
-  const uint64_t io_b = up(n * (kIn + kRes), 256);
+  const uint64_t text_b = round_up(v.thi - v.tlo, 256), sext_b = round_up(sext, 256), out_b = round_up(outb + 16, 256);
+  const uint64_t io_b = round_up(n * (kIn + kRes), 256);
   const uint64_t need = text_b + sext_b + out_b + io_b;
   std::lock_guard<std::mutex> lock(ctx->mu);
   KeepCurrentDevice keep;

@@ -97,7 +97,8 @@ def test_fused_kernel_resources(tmp_path):
                 for k in ("b64_update_lines_kernel", "b64_update_flat_kernel"))
     scan = _number(stages["b64_update_kernel"], "LDS Size [bytes/block]")
     assert 2 * 5256 <= lds <= tiles + 64 < tiles + scan - 4096, (lds, tiles, scan)
-    text = "".join(open(os.path.join(CSRC, name)).read() for name in ("b64_update_fused.hip", "b64_update_stages.hpp"))
+    text = "".join(open(os.path.join(CSRC, name)).read()
+                   for name in ("b64_update_fused.hip", "b64_update_stages.hpp", "b64_device.hpp"))
     assert "asm" not in text.replace("__launch_bounds__", "")  # no inline assembly: only barriers synchronise
     assert "while (" not in text and "__syncthreads()" in text
     # atomics go to LDS only (the scan's first '='), and every stage is stated once, in the header

@@ -1,15 +1,22 @@
 #!/usr/bin/env python3
 """Per-kernel digests of the gfx950 ISA of a HIP source (instruction lines only).
 
-    python tools/isa_digest.py [SRC] [--record tests/golden/isa_shipped.json]
+    python tools/isa_digest.py [SRC ...] [--record tests/golden/isa_shipped.json]
 
-Compiles SRC (default: the shipped bitflood_amd/csrc/sha1_kernels.hip) with the
-shipped flags to device assembly, splits it into kernels at their `.type ...,
+Compiles each SRC (default: the shipped bitflood_amd/csrc/sha1_kernels.hip) with
+the shipped flags to device assembly, splits it into kernels at their `.type ...,
 @function` / `.Lfunc_end` markers and hashes each kernel's instruction stream
 (directives, labels' own names and comments dropped; branch targets renamed to
 their order of appearance, so a renumbered label is not a change).  tests/test_isa.py
 compares the shipped kernels with the recorded digests: a refactor that moves
 code between files must leave them unchanged.
+
+One SRC is recorded as {"source", "hipcc_flags", "kernels"}; several as
+{"hipcc_flags", "sources": {source: kernels}}.  The base64 translation units
+beside sha1_kernels.hip are recorded in tests/golden/isa_b64.json:
+
+    python tools/isa_digest.py --record tests/golden/isa_b64.json \
+        bitflood_amd/csrc/{b64_update,b64_update_lines,b64_flat,b64_update_fused,b64_update_seq,b64_encode_update,b64_flat_encode}.hip
 """
 import argparse
 import hashlib
@@ -79,14 +86,19 @@ def digests(src, extra=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("src", nargs="?", default=os.path.join(CSRC, "sha1_kernels.hip"))
+    ap.add_argument("src", nargs="*", default=[os.path.join(CSRC, "sha1_kernels.hip")])
     ap.add_argument("--record", help="write the digests to this JSON file")
     a = ap.parse_args()
-    d = digests(a.src)
+    rel = [os.path.relpath(os.path.abspath(s), ROOT) for s in a.src]
+    d = {r: digests(s) for r, s in zip(rel, a.src)}
+    if len(rel) == 1:
+        d = d[rel[0]]
+        rec = {"source": rel[0], "hipcc_flags": FLAGS[:3], "kernels": d}
+    else:
+        rec = {"hipcc_flags": FLAGS[:3], "sources": d}
     if a.record:
         with open(a.record, "w") as f:
-            json.dump({"source": os.path.relpath(a.src, ROOT), "hipcc_flags": FLAGS[:3], "kernels": d}, f,
-                      indent=1, sort_keys=True)
+            json.dump(rec, f, indent=1, sort_keys=True)
             f.write("\n")
     json.dump(d, sys.stdout, indent=1)
     print()
