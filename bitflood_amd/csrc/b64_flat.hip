@@ -48,6 +48,7 @@
 #include <algorithm>
 #include <atomic>
 
+#include "b64_decode_tiles.hpp"
 #include "b64_device.hpp"
 #include "b64_flat.hpp"
 #include "b64_update_stages.hpp"
@@ -63,16 +64,7 @@ using namespace b64s;
 // from kTileText = 5184 characters.
 constexpr uint32_t kTileText = kFlatTileText;
 static_assert(kTileBytes == 3888 && kTileText == 5184, "the tile as stated above and in tests/wire_flat_model.py");
-constexpr uint32_t kTilesPerGroup = 4;  // the one-shot pass: consecutive tiles of a chunk per workgroup
-
-// The bytes of v at and past index `from` (0..16) zeroed.
-__device__ __forceinline__ uint4 zero_from(uint4 v, uint32_t from) {
-  uint32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (uint32_t m = 0; m < 16; ++m)
-    if (m >= from) ws[m >> 2] &= ~(255u << (8 * (m & 3)));
-  return make_uint4(ws[0], ws[1], ws[2], ws[3]);
-}
+constexpr uint32_t kTilesPerGroup = kFlatTilesPerGroup;  // the one-shot pass: consecutive tiles of a chunk per workgroup
 
 // ---------------------------------------------------------------------------
 // The one-shot pass.  blockIdx.x = group of tiles, blockIdx.y = chunk -

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "b64_encode_update.hpp"
 #include "lbf_hash.h"
 
 namespace lbf {
@@ -18,8 +19,9 @@ namespace lbf {
 // the encoder's.  Chunks of 54 bytes or less stay with the one-pass decode: up
 // to 53 bytes the two layouts are one text, and the 72 characters of 54 bytes
 // are a line the one-pass decode takes without its trailing separator.
-inline bool b64_flat_candidate(uint32_t text_len, uint32_t cap) {
-  return cap > 54 && text_len == 4 * (((uint64_t)cap + 2) / 3) && text_len != lbf_b64_put_length(cap);
+// (b64e::text_length(cap, false) is lbf_b64_put_length(cap); host and device: b64_decode_routed_kernel routes by it.)
+LBF_ENC_HD inline bool b64_flat_candidate(uint32_t text_len, uint32_t cap) {
+  return cap > 54 && text_len == 4 * (((uint64_t)cap + 2) / 3) && text_len != b64e::text_length(cap, false);
 }
 
 // b64_flat_decode_kernel's arrays: those of the one-pass decode (B64Launch,

@@ -48,24 +48,6 @@ using b64d::kEq;
 using b64d::kSkip;
 constexpr int kB64Threads = 256;  // one lane per entry of the decode table below
 
-struct B64Table {
-  uint8_t v[256];
-};
-
-constexpr B64Table make_b64_table() {
-  B64Table t{};
-  for (int c = 0; c < 256; ++c) t.v[c] = (uint8_t)kSkip;
-  for (int c = 'A'; c <= 'Z'; ++c) t.v[c] = (uint8_t)(c - 'A');
-  for (int c = 'a'; c <= 'z'; ++c) t.v[c] = (uint8_t)(26 + c - 'a');
-  for (int c = '0'; c <= '9'; ++c) t.v[c] = (uint8_t)(52 + c - '0');
-  t.v['+'] = 62;
-  t.v['/'] = 63;
-  t.v['='] = (uint8_t)kEq;
-  return t;
-}
-
-__constant__ B64Table g_b64_table = make_b64_table();
-
 // ---------------------------------------------------------------------------
 // Tiles of whole lines.  The encoder's text is lines of 18 groups: 72 alphabet
 // characters and a separator (base64.h:197-205's '\n', framed as a space), 73
@@ -115,161 +97,6 @@ constexpr uint32_t kDecLines = LBF_B64_DEC_LINES;
 constexpr uint32_t kDecText = kDecLines * 73, kDecBytes = kDecLines * 54, kDecGroups = kDecLines * 18;
 static_assert(kDecBytes % 16 == 0, "a decode tile is whole 16-byte blocks of output");
 
-// A tile's span staged through registers into LDS (b64_device.hpp): LDS byte (delta + k) = src[k].
-template <uint32_t kPer>
-using B64Stage = b64d::Stage<kPer, kB64Threads, 0>;
-
-// Store a 16-byte block to base + pos, clipped to [0, end) of the slot: 64-bit
-// positions, and the byte tail as the loop that stops at the slot's end.
-__device__ __forceinline__ void b64_put_block(uint8_t* base, uint64_t pos, uint64_t end, uint4 v) {
-  b64d::put_block<true, true>(base, pos, (uint64_t)0, end, v);
-}
-
-// ---------------------------------------------------------------------------
-// One pass for text laid out as the encoder writes it (round 4; tiled in
-// round 5).  Almost every frame carries exactly what xmlrpc++'s encoder
-// wrote: group g of the chunk at 4g + g/18, a separator (any character outside
-// the alphabet) after every 18th group, '=' only as "xx==" / "xxx=" in the
-// last group.  For such a text the place of every character is known without
-// a scan.  The lanes check the layout as they read it; a chunk whose text
-// breaks it anywhere (junk, a dropped or extra character, '=' elsewhere) is
-// marked in redo[] and decoded again by b64_decode_kernel, whose general rules
-// give the same result as this pass on every canonical text.
-//
-// The length gives the group count.  The encoder writes a separator after
-// every 18th complete group, so a text of G = 18q + r groups (0 < r < 18 or
-// r = 0) has length 73q + 4r, and one whose last, padded group is the 18th of
-// its line has no separator after it: 73q + 72, G = 18(q + 1).
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool b64_canon_groups(uint32_t len, uint32_t* groups) {
-  const uint32_t q = len / 73, rem = len % 73;
-  if (rem == 72) {  // the last line's 18th group is the padded last group
-    *groups = 18 * q + 18;
-    return true;
-  }
-  if (rem % 4 != 0) return false;
-  *groups = 18 * q + rem / 4;
-  return true;
-}
-
-// One block of a tile of the one-pass decode from its text in LDS (sb, from
-// byte `delta`): in pass p, lane v builds and stores bytes [16u, 16u + 16) of
-// the tile, u = v + 256p (if the tile has that block).  Returns true when the
-// lane saw a character that breaks the layout.  The kernel is VALU-bound
-// (about 70 % of its time was VALU issue at 230 instructions per block), so the
-// block keeps its instruction count down: the layout checks fold into two flag
-// words, the sextets are joined unmasked, and the 18 bytes are packed with five
-// v_perm_b32 (157 -> 133 us per 1,024 x 256 KiB).
-template <uint32_t kPass>
-__device__ __forceinline__ bool b64_decode_block(const uint8_t* sb, uint32_t delta, const uint8_t* tab, uint32_t tile,
-                                                 uint32_t groups, uint32_t len, uint64_t want, uint32_t limit,
-                                                 uint8_t* o) {
-  if (threadIdx.x + kPass * kB64Threads >= kDecBytes / 16) return false;
-  // Bytes [16u, 16u + 16) of the tile come from its groups g0 .. g0 + 5, whose
-  // characters lie in [c0, c0 + 25): 24 characters and at most one separator,
-  // after group 17 - r0 of the window when r0 >= 12.  One window of eight
-  // aligned dwords holds them; each group's four characters are cut out of it
-  // with v_alignbyte (no divergent branch: groups past the chunk's end are
-  // decoded from whatever lies there and masked below).
-  const uint32_t* w = reinterpret_cast<const uint32_t*>(sb);
-  const uint32_t b0 = 16 * (threadIdx.x + kPass * kB64Threads), g0 = b0 / 3, phase = b0 - 3 * g0;
-  const uint32_t l0 = g0 / 18, r0 = g0 - 18 * l0;
-  const uint32_t c0 = delta + 4 * g0 + l0, sh0 = c0 & 3u;
-#if LBF_B64_DEC_WIN64
-  // A/B: the window as five 8-byte reads from the even dword below it.  Lanes'
-  // windows start ~5.3 dwords apart, so eight ds_read_b32 (banks (a/4) mod 32,
-  // 32-lane groups) meet ~3-way bank conflicts; ds_read_b64 banks mod 64.
-  const uint32_t r = (c0 >> 2) & 1u;
-  const uint2* wb = reinterpret_cast<const uint2*>(w + ((c0 >> 2) & ~1u));
-  uint32_t win[10];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const uint2 x2 = wb[k];
-    win[2 * k] = x2.x;
-    win[2 * k + 1] = x2.y;
-  }
-#else
-  const uint32_t* wb = w + (c0 >> 2);
-  uint32_t win[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) win[k] = wb[k];
-#endif
-  const uint32_t gbase = tile * kDecGroups + g0;  // the chunk's index of group g0
-  bool bad = false;
-  uint32_t x[6];
-  // Table entries are 0..63, '=' 64 and anything else 255, so (entry >> 6)
-  // is 0 exactly for an alphabet character: two flag bits per group, at 2j,
-  // for all four characters (finner) and the first two (fhead).
-  uint32_t finner = 0, fhead = 0;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    const uint32_t sep = r0 + j >= 18 ? 1u : 0u;
-    const uint32_t off = sh0 + sep;  // 0..4: this group's offset from dword j of the window
-#if LBF_B64_DEC_WIN64
-    const uint32_t q = r + (off >> 2);  // 0..2 dwords past win[j]
-    const uint32_t lo = q == 0 ? win[j] : q == 1 ? win[j + 1] : win[j + 2];
-    const uint32_t hi = q == 0 ? win[j + 1] : q == 1 ? win[j + 2] : win[j + 3];
-#else
-    const uint32_t lo = off >= 4 ? win[j + 1] : win[j], hi = off >= 4 ? win[j + 2] : win[j + 1];
-#endif
-    const uint32_t c = __builtin_amdgcn_alignbyte(hi, lo, off & 3u);
-    const uint32_t s0 = tab[c & 255], s1 = tab[(c >> 8) & 255], s2 = tab[(c >> 16) & 255], s3 = tab[c >> 24];
-    const uint32_t o2 = s0 | s1, o4 = o2 | s2 | s3;
-    finner |= (o4 >> 6) << (2 * j);
-    fhead |= (o2 >> 6) << (2 * j);
-    // unmasked: an entry above 63 spoils only its own group's bytes, and such a
-    // group is either marked bad or the last group's '=' padding, whose bytes
-    // (those a '=' in character 2 or 3 reaches) lie past the decoded length
-    // and are zeroed below
-    x[j] = (((s0 << 6) | s1) << 12) | ((s2 << 6) | s3);
-  }
-  {
-    // window groups j < rel lie inside the text (all four characters in the
-    // alphabet); group rel is the chunk's last (its first two in the alphabet;
-    // the kernel checks its padding)
-    const int32_t rel = (int32_t)groups - 1 - (int32_t)gbase;
-    const uint32_t nin = (uint32_t)min(max(rel, 0), 6);
-    const uint32_t inner_mask = (1u << (2 * nin)) - 1u;
-    const uint32_t head_mask = rel >= 0 && rel < 6 ? 3u << (2 * rel) : 0u;
-    bad |= ((finner & inner_mask) | (fhead & head_mask)) != 0;
-  }
-  // the separator after group 17 - r0 (when in the window): any character outside the alphabet
-  {
-    const uint32_t js = 17 - r0;  // < 6 when r0 >= 12
-    const uint32_t gs = gbase + js;
-    const uint32_t at = (c0 & ~3u) + min(sh0 + 4 * js + 4, 31u);
-    const bool check = r0 >= 12 && 4 * gs + gs / 18 + 4 < len;
-    bad |= check && tab[sb[at]] != kSkip;
-  }
-  uint4 v = b64d::pack16(x, phase);  // the 18 bytes of the six groups, cut to the block's 16
-  const uint64_t pos = (uint64_t)tile * kDecBytes + b0;
-  if (pos < limit) {
-    if (pos + 16 > want) {  // the decoded bytes end inside this block: zero the rest of the slot
-      uint32_t ws[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-      for (int m = 0; m < 16; ++m)
-        if (pos + m >= want) ws[m >> 2] &= ~(255u << (8 * (m & 3)));
-      v = make_uint4(ws[0], ws[1], ws[2], ws[3]);
-    }
-    b64_put_block(o, pos, limit, v);
-  }
-  return bad;
-}
-
-// A tile: every lane its block of each pass (one pass for the shipped 243-block
-// tile; the block index is written out in each pass rather than passed in, which
-// kept the shipped kernel at 71 VGPRs where a block-index argument made it 87).
-__device__ __forceinline__ bool b64_decode_tile(const uint8_t* sb, uint32_t delta, const uint8_t* tab, uint32_t tile,
-                                                uint32_t groups, uint32_t len, uint64_t want, uint32_t limit,
-                                                uint8_t* o) {
-  static_assert(kDecBytes / 16 <= 3 * kB64Threads, "three blocks per lane at most");
-  bool bad = b64_decode_block<0>(sb, delta, tab, tile, groups, len, want, limit, o);
-  if constexpr (kDecBytes / 16 > kB64Threads) bad |= b64_decode_block<1>(sb, delta, tab, tile, groups, len, want, limit, o);
-  if constexpr (kDecBytes / 16 > 2 * kB64Threads)
-    bad |= b64_decode_block<2>(sb, delta, tab, tile, groups, len, want, limit, o);
-  return bad;
-}
-
 // Tiles per workgroup: a workgroup takes kDecTilesPerGroup (kEncTilesPerGroup) consecutive tiles
 // of its chunk and double-buffers them in LDS, so the next tile's loads are in
 // flight while it decodes (or encodes) the current one: one barrier per tile,
@@ -281,6 +108,39 @@ __device__ __forceinline__ bool b64_decode_tile(const uint8_t* sb, uint32_t delt
 #define LBF_B64_ENC_TILES_PER_GROUP 2  // of 112 lines (1 and 3: 0.5-1 % slower; 64-line tiles: 4, eight 5 % slower)
 #endif
 constexpr uint32_t kDecTilesPerGroup = LBF_B64_DEC_TILES_PER_GROUP, kEncTilesPerGroup = LBF_B64_ENC_TILES_PER_GROUP;
+
+}  // namespace
+}  // namespace lbf
+
+// The staging, the one-pass decode's length rule, block and tile are
+// b64_decode_tiles.hpp's, which b64_decode_routed_kernel (b64_verify_launch.hip)
+// is built from too.  That header states the geometry above itself for a unit
+// that does not include this one (this header holds kernels), and holds the
+// two statements together with static_asserts on the values.
+#define LBF_B64_TILE_GEOMETRY_STATED
+#include "b64_decode_tiles.hpp"
+
+namespace lbf {
+namespace {
+
+struct B64Table {
+  uint8_t v[256];
+};
+
+constexpr B64Table make_b64_table() {
+  B64Table t{};
+  for (int c = 0; c < 256; ++c) t.v[c] = (uint8_t)kSkip;
+  for (int c = 'A'; c <= 'Z'; ++c) t.v[c] = (uint8_t)(c - 'A');
+  for (int c = 'a'; c <= 'z'; ++c) t.v[c] = (uint8_t)(26 + c - 'a');
+  for (int c = '0'; c <= '9'; ++c) t.v[c] = (uint8_t)(52 + c - '0');
+  t.v['+'] = 62;
+  t.v['/'] = 63;
+  t.v['='] = (uint8_t)kEq;
+  return t;
+}
+
+__constant__ B64Table g_b64_table = make_b64_table();
+
 
 // blockIdx.x = group of tiles, blockIdx.y = chunk - chunk0.  Chunk i's text is
 // text[text_off[i] .. + text_len[i]); its decoded bytes go to

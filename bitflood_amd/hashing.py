@@ -728,6 +728,26 @@ def verify_encode_b64_launch(base, offsets, sizes, n, max_size, text, text_offse
                                               p(verdicts), _layout(layout), p(text), p(text_offsets), stream))
 
 
+def b64_verify_launch_work(n: int) -> int:
+    """lbf_b64_verify_launch_work: the bytes of `work` verify_b64_launch needs for n chunks."""
+    return int(load().lbf_b64_verify_launch_work(n))
+
+
+def verify_b64_launch(text, text_offsets, text_lens, n, max_text_len, expected_sizes, max_size, out, out_offsets,
+                      out_sizes, work, digests=None, expected=None, verdicts=None, stream=None):
+    """lbf_b64_verify_launch: chunk text in device memory (either peer layout, or
+    anything else, mixed in one call) decoded into its slots and verified,
+    asynchronous on `stream`; max_text_len and max_size are the longest text and
+    the largest expected size and size the grids.  `work` is
+    b64_verify_launch_work(n) bytes: behind the call work[0, n) is `over` and
+    work[n, 2n) is `redo` (1 = the chunk went to the general scan).  digests, or
+    expected + verdicts, may be None; with none of them the call only decodes."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_b64_verify_launch(p(text), p(text_offsets), p(text_lens), n, max_text_len, p(expected_sizes),
+                                       max_size, p(out), p(out_offsets), p(out_sizes), p(digests), p(expected),
+                                       p(verdicts), p(work), stream))
+
+
 def set_b64_lines(on) -> bool:
     """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
     off, process-wide; returns the previous setting."""
@@ -761,6 +781,7 @@ __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode",
            "uniform_launch", "batch_launch", "update_launch", "STATE_DTYPE", "new_states",
            "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "B64_ENC_STATE_DTYPE", "new_b64_enc_states",
            "b64_text_length", "b64_encode_update_launch", "verify_encode_b64_launch",
+           "verify_b64_launch", "b64_verify_launch_work",
            "chain_table", "update_seq_launch", "b64_update_seq_launch",
            "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -668,6 +668,54 @@ int lbf_verify_encode_b64_launch(const uint8_t* d_data, const uint64_t* d_offset
                                  uint32_t max_size, uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                                  int layout, char* d_text, const uint64_t* d_text_offsets, void* stream);
 
+/* ---- received chunk text resident in device memory, one-shot ---------------
+ * lbf_b64_verify_batch for text that already lies in device memory,
+ * asynchronous on `stream`: only enqueues -- no allocation, no
+ * synchronisation, no context, no host round trip.  All pointers are device
+ * memory on the current device.  Chunk i's text is d_text[d_text_offsets[i],
+ * + d_text_lens[i]), in either peer layout (xmlrpc++'s lines, or the unbroken
+ * RFC 4648 text of the Java and Perl peers) or anything else, chunks of all
+ * kinds in one call in any order; it is decoded by xmlrpc++'s rule, exactly as
+ * lbf_b64_verify_batch decodes it.  The bytes land at d_out[d_out_offsets[i],
+ * + d_expected_sizes[i]); the rest of the slot past the decoded length is
+ * zeroed, and nothing outside the slots is written.  d_out_sizes[i] = the
+ * decoded length, or d_expected_sizes[i] + 1 when the text decodes to more.
+ * d_verdicts[i] = 1 only when the decoded length is d_expected_sizes[i] and
+ * the SHA-1 of the bytes equals d_expected[20*i ..); d_digests + 20*i receives
+ * the SHA-1 of the min(decoded, expected) bytes in the slot.  d_expected and
+ * d_verdicts go together and both may be NULL; d_digests may be NULL; with all
+ * three NULL nothing is hashed.  d_out, d_out_offsets, d_out_sizes and d_work
+ * (lbf_b64_verify_launch_work(n) = 2 * n bytes) are required.
+ * The host cannot read the tables, so max_text_len and max_size -- the longest
+ * text and the largest expected size of the call, at most 1.5 GiB and 1 GiB --
+ * size the grids.  A chunk over either bound is not decoded: its slot is
+ * untouched, d_out_sizes[i] = UINT32_MAX, its verdict is 0 (its digest is the
+ * empty string's).  The route is decided per chunk on the device from its own
+ * lengths and does not depend on lbf_set_b64_flat: a chunk of more than 54
+ * bytes whose text length is 4 * ceil(size / 3) and not lbf_b64_put_length(size)
+ * takes the flat tiles, any other the encoder-layout tiles, and a text either
+ * cannot take goes to a general scan.  d_work is zeroed first and then holds
+ * two arrays a caller (or a test) may read behind the call: d_work[0, n) is
+ * `over` (1 = the text decodes to more than the slot), d_work[n, 2n) is `redo`
+ * (1 = the chunk went to the general scan).
+ * What the launch cannot check for itself is the caller's responsibility: slots
+ * that overlap one another, and text that overlaps the output (undefined, but
+ * nothing outside the slots and the tables is written); and calls on different
+ * streams need different d_work (and different outputs).
+ * Refused with LBF_ERR_INVALID before anything is enqueued: a NULL required
+ * argument, n over 2^31-1, max_size over 1 GiB or max_text_len over 1.5 GiB,
+ * d_expected without d_verdicts or the reverse, digest or expected arrays that
+ * are not 4-byte aligned, a table that is not aligned to its element size or
+ * does not fit the allocation it points into.  n == 0 returns LBF_OK whatever
+ * else is passed and enqueues nothing. */
+uint64_t lbf_b64_verify_launch_work(uint64_t n);   /* bytes of d_work: 2 * n */
+int lbf_b64_verify_launch(const char* d_text, const uint64_t* d_text_offsets, const uint32_t* d_text_lens,
+                          uint64_t n, uint32_t max_text_len,
+                          const uint32_t* d_expected_sizes, uint32_t max_size,
+                          uint8_t* d_out, const uint64_t* d_out_offsets, uint32_t* d_out_sizes,
+                          uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
+                          uint8_t* d_work, void* stream);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */
