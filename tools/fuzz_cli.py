@@ -9,7 +9,7 @@ file (flipped bytes, a truncation, an appended tail, deletion, or nothing) and
 checks lbf_verify's chunkmap, verified count, to_download count and content
 hash against what Flood.cpp:220-299 implies for those bytes.
 
-Usage: python tools/fuzz_cli.py [--seconds 120] [--seed 1]
+Usage: python tools/fuzz_cli.py [--seconds 120] [--seed 1] [--cases N]
 """
 import argparse
 import base64
@@ -107,13 +107,14 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=120)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--cases", type=int, default=1 << 30, help="stop after this many cases (a deterministic count)")
     ap.add_argument("--replay", type=int, default=None)
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="lbf_cli_fuzz_")
     t0, k, rc = time.time(), 0, 0
     try:
         seeds = [a.replay] if a.replay is not None else None
-        while (seeds and k < 1) or (not seeds and time.time() - t0 < a.seconds):
+        while (seeds and k < 1) or (not seeds and k < a.cases and time.time() - t0 < a.seconds):
             seed = seeds[0] if seeds else a.seed * 1_000_003 + k
             fail = one_case(seed, tmp)
             if fail:

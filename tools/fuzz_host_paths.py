@@ -10,7 +10,7 @@ multi-file batches (lbf_files_ranges) over 2-40 files, some missing in verify
 mode, with a random LBF_FILES_WINDOW so floods run in windows of files.  The copy-thread count is process-wide (LBF_COPY_THREADS), so run the
 tool once per setting.  Everything is checked against the oracle restatement.
 
-Usage: LBF_COPY_THREADS=3 python tools/fuzz_host_paths.py [--seconds 60] [--seed 1]
+Usage: LBF_COPY_THREADS=3 python tools/fuzz_host_paths.py [--seconds 60] [--seed 1] [--cases N]
 """
 import argparse
 import ctypes
@@ -182,6 +182,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--cases", type=int, default=1 << 30, help="stop after this many cases (a deterministic count)")
     ap.add_argument("--replay", type=int, default=None, help="re-run one case seed, print mismatches")
     a = ap.parse_args()
     global DIAG
@@ -202,7 +203,7 @@ def main():
         if a.replay is not None:
             print(json.dumps({"replay": a.replay, "result": one_case(a.replay, orc, hashers, pool, path, tmpdir)}))
             a.seconds = 0
-        while time.time() - t0 < a.seconds:
+        while k < a.cases and time.time() - t0 < a.seconds:
             seed = a.seed * 1_000_003 + k
             slot, mode, n, ok = one_case(seed, orc, hashers, pool, path, tmpdir)
             stats[f"slot{slot}m{mode}"] = stats.get(f"slot{slot}m{mode}", 0) + 1
