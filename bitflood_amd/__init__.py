@@ -12,7 +12,7 @@ from . import _capi  # noqa: F401  (imports torch first: one HIP runtime per pro
 from .hashing import (B64_ENC_STATE_DTYPE, B64_STATE_DTYPE, STATE_DTYPE, ChunkHasher, DeviceBuffer,  # noqa: F401
                       LbfError, b64_27, b64_27_decode, b64_encode_update_launch, b64_text_length, b64_update_launch,
                       b64_update_seq_launch, b64_verify_launch_work, chain_table, chunk_table, new_b64_enc_states, new_b64_states,
-                      new_states, set_b64_flat, set_b64_fused, set_b64_lines, update_seq_launch,
-                      verify_b64_launch, verify_encode_b64_launch)
+                      new_states, set_b64_flat, set_b64_fused, set_b64_lines, sha1_hashes_launch, update_seq_launch,
+                      verify_b64_launch, verify_encode_b64_launch, verify_hashes_launch, verify_hashes_launch_work)
 
 __version__ = "0.1.0"

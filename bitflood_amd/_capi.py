@@ -70,6 +70,12 @@ _SIGS = {
     "lbf_b64_verify_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_uint32, _c.c_void_p,
                                          _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_sha1_hashes_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
+                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_verify_hashes_launch_work": (_c.c_uint64, [_c.c_uint64]),
+    "lbf_verify_hashes_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
+                                            _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                            _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_b64_put_length": (_c.c_uint64, [_c.c_uint64]),
     "lbf_b64_verify_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                         _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,

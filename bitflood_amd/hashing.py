@@ -748,6 +748,43 @@ def verify_b64_launch(text, text_offsets, text_lens, n, max_text_len, expected_s
                                        p(verdicts), p(work), stream))
 
 
+# hash_text.hpp's kMapBlock and kScanWidth: the chunks a workgroup of the
+# chunkmap kernels takes, and the workgroup counts the scan takes a trip
+HASH_TEXT_MAP_BLOCK = 1024
+HASH_TEXT_SCAN_WIDTH = 1024
+
+
+def verify_hashes_launch_work(n: int) -> int:
+    """lbf_verify_hashes_launch_work: the bytes of `work` sha1_hashes_launch and
+    verify_hashes_launch need for n chunks."""
+    return int(load().lbf_verify_hashes_launch_work(n))
+
+
+def sha1_hashes_launch(base, offsets, sizes, n, hashes, work, hash_offsets=None, digests=None, stream=None):
+    """lbf_sha1_hashes_launch: chunks in device memory hashed and their
+    27-character hash strings (the flood file's form, no NUL) written at
+    hashes + hash_offsets[i], or packed at 27 * i when hash_offsets is None,
+    asynchronous on `stream`; nothing outside the slots is written.  `work` is
+    verify_hashes_launch_work(n) bytes; the digests land in `digests`, or in
+    `work` when it is None."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_sha1_hashes_launch(p(base), p(offsets), p(sizes), n, p(hashes), p(hash_offsets), p(digests),
+                                        p(work), stream))
+
+
+def verify_hashes_launch(base, offsets, sizes, n, hashes, chunkmap, work, hash_offsets=None, hash_lens=None,
+                         missing=None, missing_count=None, digests=None, stream=None):
+    """lbf_verify_hashes_launch: chunks in device memory hashed and compared, as
+    strings, with the flood file's hashes (hashes + hash_offsets[i], hash_lens[i]
+    characters; both None for packed 27-character strings), asynchronous on
+    `stream`.  chunkmap[i] = '1' for an equal string of length 27, else '0';
+    missing[0, missing_count[0]) receives the indices with '0' in ascending
+    order (both may be None).  `work` is verify_hashes_launch_work(n) bytes."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_verify_hashes_launch(p(base), p(offsets), p(sizes), n, p(hashes), p(hash_offsets), p(hash_lens),
+                                          p(chunkmap), p(missing), p(missing_count), p(digests), p(work), stream))
+
+
 def set_b64_lines(on) -> bool:
     """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
     off, process-wide; returns the previous setting."""
@@ -782,6 +819,8 @@ __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode",
            "B64_STATE_DTYPE", "new_b64_states", "b64_update_launch", "B64_ENC_STATE_DTYPE", "new_b64_enc_states",
            "b64_text_length", "b64_encode_update_launch", "verify_encode_b64_launch",
            "verify_b64_launch", "b64_verify_launch_work",
+           "sha1_hashes_launch", "verify_hashes_launch", "verify_hashes_launch_work",
+           "HASH_TEXT_MAP_BLOCK", "HASH_TEXT_SCAN_WIDTH",
            "chain_table", "update_seq_launch", "b64_update_seq_launch",
            "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -716,6 +716,62 @@ int lbf_b64_verify_launch(const char* d_text, const uint64_t* d_text_offsets, co
                           uint8_t* d_digests, const uint8_t* d_expected, uint8_t* d_verdicts,
                           uint8_t* d_work, void* stream);
 
+/* ---- the flood file's hash strings on the device ---------------------------
+ * bitflood names a chunk by the 27 characters lbf_b64_27 gives for its SHA-1.
+ * These two launches keep that form on the device for chunks resident in
+ * device memory: Encoder::EncodeFile's strings out, and the resume / seed
+ * verify of Flood::_SetupFilesAndChunks (Flood.cpp:259-285) -- string compare,
+ * chunkmap, chunks to download -- with no host step before or behind the hash.
+ * All pointers are device memory on the current device.  Both calls only
+ * enqueue on `stream`: no allocation, no synchronisation, no context, no host
+ * read of any table.  Chunk i = d_data[d_offsets[i], + d_sizes[i]), hashed by
+ * lbf_sha1_launch itself (the usual kernel selection, lbf_set_kernel_variant
+ * included; a chunk of size 0 hashes as the empty string) into d_digests, or
+ * into d_work when d_digests is NULL.  d_work is
+ * lbf_verify_hashes_launch_work(n) bytes for both calls, 4-byte aligned:
+ *   ((20 * n + 15) & ~15) + 4 * ceil(n / 1024)
+ * -- the digests, then from the next multiple of 16 one uint32 per 1,024
+ * chunks (the count of '0' of that group, then its base in the list).  Calls
+ * on different streams need different d_work.
+ *
+ * lbf_sha1_hashes_launch: string i, 27 characters and no NUL, is written at
+ * d_hashes[d_hash_offsets[i], + 27), or at 27 * i when d_hash_offsets is NULL.
+ * No other byte of d_hashes is written, so a slot may sit at any byte phase,
+ * inside a preformatted hash="..." attribute for example.
+ *
+ * lbf_verify_hashes_launch: hash i is d_hashes[d_hash_offsets[i],
+ * + d_hash_lens[i]); both tables may be NULL together, which means packed
+ * 27-byte strings.  d_chunkmap[i] = '1' exactly when d_hash_lens[i] == 27 and
+ * the 27 bytes equal the string of chunk i's SHA-1, and '0' in every other
+ * case: any other length (0 included), a byte outside the alphabet, a last
+ * character with non-zero low bits, another chunk's hash.  The characters are
+ * compared, not decoded digests, as chunk.m_hash.compare(test) == 0 does.
+ * d_missing and d_missing_count go together and may both be NULL; otherwise
+ * d_missing[0, *d_missing_count) holds the indices with '0' in ascending order
+ * (d_missing has room for n entries; those past the count are untouched), and
+ * *d_missing_count is written by every call with n > 0, also when it is 0.
+ * A flood of several files passes its chunks in the flood's order (map order
+ * of the file names, then chunk index): each file's chunkmap is then a
+ * contiguous slice of d_chunkmap, and the caller maps the list's entries back
+ * to (name, index).
+ *
+ * Refused with LBF_ERR_INVALID before anything is enqueued: a NULL d_data,
+ * d_offsets, d_sizes, d_hashes, d_work or (verify) d_chunkmap, n over 2^31-1,
+ * d_hash_offsets without d_hash_lens or d_missing without d_missing_count or
+ * the reverse, d_digests or d_work not 4-byte aligned, a table that is not
+ * aligned to its element size or does not fit the allocation it points into
+ * (strings addressed through d_hash_offsets are the caller's to place).
+ * n == 0 returns LBF_OK, enqueues nothing and writes nothing,
+ * *d_missing_count included. */
+int lbf_sha1_hashes_launch(const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t n,
+                           char* d_hashes, const uint64_t* d_hash_offsets /* NULL: 27 * i */,
+                           uint8_t* d_digests /* may be NULL */, uint8_t* d_work, void* stream);
+uint64_t lbf_verify_hashes_launch_work(uint64_t n);   /* bytes of d_work, for both calls */
+int lbf_verify_hashes_launch(const uint8_t* d_data, const uint64_t* d_offsets, const uint32_t* d_sizes, uint64_t n,
+                             const char* d_hashes, const uint64_t* d_hash_offsets, const uint32_t* d_hash_lens,
+                             char* d_chunkmap, uint32_t* d_missing, uint32_t* d_missing_count,
+                             uint8_t* d_digests /* may be NULL */, uint8_t* d_work, void* stream);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */
