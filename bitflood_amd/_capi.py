@@ -76,6 +76,15 @@ _SIGS = {
     "lbf_verify_hashes_launch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p,
                                             _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
                                             _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_wire_frames_launch_work": (_c.c_uint64, [_c.c_uint64]),
+    "lbf_wire_frames_launch": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p,
+                                          _c.c_void_p, _c.c_void_p, _c.c_void_p]),
+    "lbf_wire_send_chunks_launch_work": (_c.c_uint64, [_c.c_uint64]),
+    "lbf_wire_send_chunks_launch": (_c.c_int, [_c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_uint32,
+                                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint32,
+                                               _c.c_void_p, _c.c_void_p, _c.c_uint32, _c.c_void_p, _c.c_void_p,
+                                               _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_void_p,
+                                               _c.c_uint32, _c.c_void_p, _c.c_void_p, _c.c_void_p]),
     "lbf_b64_put_length": (_c.c_uint64, [_c.c_uint64]),
     "lbf_b64_verify_batch": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_uint64, _c.c_void_p, _c.c_void_p,
                                         _c.c_uint64, _c.c_void_p, _c.c_void_p, _c.c_void_p, _c.c_uint64,

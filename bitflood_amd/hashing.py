@@ -785,6 +785,93 @@ def verify_hashes_launch(base, offsets, sizes, n, hashes, chunkmap, work, hash_o
                                           p(chunkmap), p(missing), p(missing_count), p(digests), p(work), stream))
 
 
+# wire_frames.hpp's geometry: the bytes of the stream a workgroup of the split
+# kernels takes, the bytes a trip of the locate kernel's search takes, the
+# frames a workgroup of the bind kernels takes, the counts the scan takes a trip
+WIRE_SPLIT_BLOCK = 4096
+WIRE_SEARCH_TRIP = 4096
+WIRE_BIND_BLOCK = 256
+WIRE_SCAN_WIDTH = 1024
+LBF_FRAME_OTHER, LBF_FRAME_SEND_CHUNK, LBF_FRAME_SEND_CHUNK_UNBOUND = 0, 1, 2
+# lbf_wire_frame
+WIRE_FRAME_DTYPE = np.dtype([("text_offset", "<u8"), ("name_offset", "<u8"), ("text_len", "<u4"), ("name_len", "<u4"),
+                             ("index", "<u4"), ("kind", "<u4")])
+
+
+def wire_frames_launch_work(stream_len: int) -> int:
+    """lbf_wire_frames_launch_work: the bytes of `work` wire_frames_launch needs
+    for a stream of stream_len bytes, 4 * ceil((stream_len + 15) / 4096)."""
+    return int(load().lbf_wire_frames_launch_work(stream_len))
+
+
+def wire_send_chunks_launch_work(n_frames: int) -> int:
+    """lbf_wire_send_chunks_launch_work: the bytes of `work` wire_send_chunks_launch
+    needs for n_frames frames, 4 * n_frames + 4 * ceil(n_frames / 256)."""
+    return int(load().lbf_wire_send_chunks_launch_work(n_frames))
+
+
+def wire_frames_launch(stream_buf, stream_len, frame_offsets, frame_lens, max_frames, n_frames, tail, work,
+                       stream=None):
+    """lbf_wire_frames_launch: the receive stream stream_buf[0, stream_len) in
+    device memory split on '\\n', asynchronous on `stream`: the first max_frames
+    frames to frame_offsets (uint64) / frame_lens (uint32), the number found to
+    n_frames[0] (uint32), the start of the unfinished last frame to tail[0]
+    (uint64).  frame_offsets and frame_lens may be None with max_frames == 0.
+    `work` is wire_frames_launch_work(stream_len) bytes."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_wire_frames_launch(p(stream_buf), stream_len, p(frame_offsets), p(frame_lens), max_frames,
+                                        p(n_frames), p(tail), p(work), stream))
+
+
+def wire_send_chunks_launch(stream_buf, stream_len, frame_offsets, frame_lens, n_frames, frames, work,
+                            live_frames=None, file_names=None, file_name_offsets=None, file_first=None, n_files=0,
+                            chunk_sizes=None, chunk_expected=None, n_chunks=0, text_offsets=None, text_lens=None,
+                            expected_sizes=None, expected=None, chunk_of=None, frame_of=None, max_chunks=0,
+                            n_located=None, stream=None):
+    """lbf_wire_send_chunks_launch: PeerWire::LocateSendChunk on every live frame
+    of the stream in device memory (the first min(live_frames[0], n_frames), or
+    n_frames when live_frames is None) into frames (WIRE_FRAME_DTYPE), bound to
+    the flood table (wire_flood_table's five arrays, or none) and compacted into
+    the dense tables verify_b64_launch reads (or none), asynchronous on
+    `stream`.  `work` is wire_send_chunks_launch_work(n_frames) bytes."""
+    p = lambda x: None if x is None else (x.ptr if isinstance(x, DeviceBuffer) else x)  # noqa: E731
+    check(load().lbf_wire_send_chunks_launch(p(stream_buf), stream_len, p(frame_offsets), p(frame_lens), n_frames,
+                                             p(live_frames), p(file_names), p(file_name_offsets), p(file_first),
+                                             n_files, p(chunk_sizes), p(chunk_expected), n_chunks, p(frames),
+                                             p(text_offsets), p(text_lens), p(expected_sizes), p(expected),
+                                             p(chunk_of), p(frame_of), max_chunks, p(n_located), p(work), stream))
+
+
+def xml_encode(name: bytes | str) -> bytes:
+    """XmlRpcUtil::xmlEncode as PeerWire::XmlEncode has it: the five characters
+    < > & ' " as their entities, every other byte as it is."""
+    raw = name.encode() if isinstance(name, str) else bytes(name)
+    ent = {ord("<"): b"&lt;", ord(">"): b"&gt;", ord("&"): b"&amp;", ord("'"): b"&apos;", ord('"'): b"&quot;"}
+    return b"".join(ent.get(c, bytes([c])) for c in raw)
+
+
+def wire_flood_table(files):
+    """The flood table wire_send_chunks_launch binds against, from
+    [(name, sizes, digests)] in the flood's order (digests: 20 bytes per chunk,
+    as bytes objects or an (n, 20) array): (file_names uint8, file_name_offsets
+    uint32[n_files + 1], file_first uint32[n_files + 1], chunk_sizes uint32,
+    chunk_expected uint8[20 * n_chunks]), host arrays ready to upload."""
+    names, name_off, first, sizes, digests = [], [0], [0], [], []
+    for name, file_sizes, file_digests in files:
+        file_sizes = [int(x) for x in file_sizes]
+        file_digests = [bytes(bytearray(d)) for d in file_digests]
+        if len(file_sizes) != len(file_digests) or any(len(d) != 20 for d in file_digests):
+            raise ValueError("wire_flood_table: one 20-byte digest per chunk size")
+        names.append(xml_encode(name))
+        name_off.append(name_off[-1] + len(names[-1]))
+        first.append(first[-1] + len(file_sizes))
+        sizes += file_sizes
+        digests += file_digests
+    return (np.frombuffer(b"".join(names), np.uint8).copy(), np.array(name_off, np.uint32),
+            np.array(first, np.uint32), np.array(sizes, np.uint32),
+            np.frombuffer(b"".join(digests), np.uint8).copy())
+
+
 def set_b64_lines(on) -> bool:
     """lbf_set_b64_lines: the line path of update_text / b64_update_launch on or
     off, process-wide; returns the previous setting."""
@@ -821,6 +908,9 @@ __all__ = ["ChunkHasher", "DeviceBuffer", "LbfError", "b64_27", "b64_27_decode",
            "verify_b64_launch", "b64_verify_launch_work",
            "sha1_hashes_launch", "verify_hashes_launch", "verify_hashes_launch_work",
            "HASH_TEXT_MAP_BLOCK", "HASH_TEXT_SCAN_WIDTH",
+           "wire_frames_launch", "wire_frames_launch_work", "wire_send_chunks_launch", "wire_send_chunks_launch_work",
+           "WIRE_FRAME_DTYPE", "WIRE_SPLIT_BLOCK", "WIRE_SEARCH_TRIP", "WIRE_BIND_BLOCK", "WIRE_SCAN_WIDTH",
+           "LBF_FRAME_OTHER", "LBF_FRAME_SEND_CHUNK", "LBF_FRAME_SEND_CHUNK_UNBOUND", "xml_encode", "wire_flood_table",
            "chain_table", "update_seq_launch", "b64_update_seq_launch",
            "set_b64_lines", "set_b64_flat", "set_b64_fused", "synchronize", "set_kernel_variant", "LBF_DEVICE_PTR",
            "_capi"]

@@ -17,6 +17,7 @@
 
 #include "lbf_hash.h"
 #include "libBitFlood/Encoder.H"
+#include "libBitFlood/PeerWire.H"
 
 namespace libBitFlood {
 
@@ -72,6 +73,33 @@ std::shared_ptr<lbf_ctx> Flood::Ctx() const {
 std::string Flood::PathOf(const std::string& i_name) const {
   if (m_rootdir.empty() || (!i_name.empty() && i_name[0] == '/')) return i_name;
   return m_rootdir + "/" + i_name;
+}
+
+Error::ErrorCode Flood::WireTable(WireFloodTable& o_table) const {
+  o_table = WireFloodTable();
+  if (!m_floodfile) return Error::UNKNOWN_ERROR_LBF;
+  WireFloodTable t;
+  t.m_nameoffsets.push_back(0);
+  t.m_first.push_back(0);
+  for (const auto& kv : m_floodfile->m_files) {
+    const FloodFile::File& file = *kv.second;
+    const size_t n = file.m_chunks.size(), first = t.m_sizes.size();
+    t.m_sizes.resize(first + n, 0);
+    t.m_expected.resize(20 * (first + n), 0);
+    std::vector<bool> seen(n, false);
+    for (const FloodFile::Chunk& c : file.m_chunks) {
+      if (c.m_index >= n || seen[c.m_index]) return Error::UNKNOWN_ERROR_LBF;
+      seen[c.m_index] = true;
+      t.m_sizes[first + c.m_index] = c.m_size;
+      U8* const digest = &t.m_expected[20 * (first + c.m_index)];
+      if (!decode_hash(c.m_hash, digest)) std::fill(digest, digest + 20, (U8)0);
+    }
+    t.m_names += PeerWire::XmlEncode(file.m_name);
+    t.m_nameoffsets.push_back((U32)t.m_names.size());
+    t.m_first.push_back((U32)t.m_sizes.size());
+  }
+  o_table = std::move(t);
+  return Error::NO_ERROR_LBF;
 }
 
 Error::ErrorCode Flood::Initialize(FloodFileSPtr& i_floodfile) {

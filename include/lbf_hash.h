@@ -772,6 +772,107 @@ int lbf_verify_hashes_launch(const uint8_t* d_data, const uint64_t* d_offsets, c
                              char* d_chunkmap, uint32_t* d_missing, uint32_t* d_missing_count,
                              uint8_t* d_digests /* may be NULL */, uint8_t* d_work, void* stream);
 
+/* ---- a receive stream on the device: frames, SendChunk frames, chunks ------
+ * lbf_b64_verify_launch takes tables in device memory that name each chunk's
+ * text, size and hash.  These two launches fill them from the raw bytes a
+ * receiver holds in device memory, so that stream -> bytes and verdicts needs
+ * no host read in between: the '\n' frame split of the peer loop, and
+ * PeerWire::LocateSendChunk on every frame, which is the specification of the
+ * second call -- kind, index, text range and name range agree with it on every
+ * frame, well-formed or not.  All pointers are device memory on the current
+ * device.  Both calls only enqueue on `stream`: no allocation, no
+ * synchronisation, no context, no host read of any table.  Calls on different
+ * streams need different d_work.
+ *
+ * lbf_wire_frames_launch splits d_stream[0, stream_len) on '\n'.  Frame k is
+ * the bytes between delimiter k-1 and delimiter k, without the delimiter; an
+ * empty frame is a frame of length 0.  The first min(found, max_frames) frames
+ * are written in stream order to d_frame_offsets / d_frame_lens (entries past
+ * that are untouched), *d_n_frames is the number found, also when it exceeds
+ * max_frames, and *d_tail is the offset of the first byte behind the last
+ * delimiter (0 when there is none, stream_len when the stream ends in one):
+ * the unfinished frame the receiver carries into its next pass.  max_frames ==
+ * 0 with both tables NULL counts only.  The stream may start and end at any
+ * byte phase; no byte outside it is read for its value.  d_work is
+ * lbf_wire_frames_launch_work(stream_len) bytes, 4-byte aligned:
+ *   4 * ceil((stream_len + 15) / 4096)
+ * -- one uint32 per 4,096 bytes, counted from the aligned 16-byte block that
+ * holds the stream's first byte.  Refused with LBF_ERR_INVALID before anything
+ * is enqueued: a NULL d_stream, d_n_frames, d_tail or d_work, stream_len over
+ * 2^32-1 (a larger arena is passed as windows), one of d_frame_offsets,
+ * d_frame_lens and max_frames without the others, a table that is not aligned
+ * to its element size or does not fit the allocation it points into.
+ * stream_len == 0 returns LBF_OK, enqueues nothing and writes nothing.
+ *
+ * lbf_wire_send_chunks_launch looks at the live frames: the first
+ * min(*d_n_frames, n_frames), or n_frames when d_n_frames is NULL.  d_frames[i]
+ * is written for each of them (entries past the live count are untouched):
+ * LBF_FRAME_OTHER with every other field 0 where LocateSendChunk returns false
+ * (or the frame is longer than 1.5 GiB + 64 KiB, or not inside the stream:
+ * such a frame is not read); otherwise the ranges as offsets into d_stream,
+ * the name as it stands in the frame, still XML-escaped.
+ * The flood table (all NULL / 0 together) names the files in the flood's order
+ * as lbf_verify_hashes_launch takes them: file f's name, in XmlEncode form, is
+ * d_file_names[d_file_name_offsets[f], d_file_name_offsets[f+1]), its chunks
+ * are the global numbers [d_file_first[f], d_file_first[f+1]), and chunk c has
+ * d_chunk_sizes[c] bytes and the digest d_chunk_expected[20 c, + 20).  A
+ * located frame is LBF_FRAME_SEND_CHUNK when its raw name bytes equal a file's
+ * entry, its index is below that file's chunk count and the global number is
+ * below n_chunks; otherwise LBF_FRAME_SEND_CHUNK_UNBOUND (a name escaped in
+ * another way included: that frame is the host's to handle).
+ * The dense tables (all NULL / 0 together) receive the bound frames in frame
+ * order, entry j < max_chunks: d_text_offsets[j], d_text_lens[j],
+ * d_expected_sizes[j], d_expected[20 j, + 20), d_chunk_of[j] (the global chunk
+ * number) and d_frame_of[j].  *d_n_located is the number bound, also when it
+ * exceeds max_chunks.  Entries [min(located, max_chunks), max_chunks) are made
+ * neutral by every call: offset 0, text length 0, expected size 0, an all-zero
+ * digest (not SHA-1 of the empty string, so the verdict is 0), d_chunk_of =
+ * d_frame_of = UINT32_MAX.  lbf_b64_verify_launch(d_stream, d_text_offsets,
+ * d_text_lens, max_chunks, ...) can therefore be enqueued straight behind it,
+ * whatever arrived.  Two frames for one chunk both appear.  d_work is
+ * lbf_wire_send_chunks_launch_work(n_frames) bytes, 4-byte aligned:
+ *   4 * n_frames + 4 * ceil(n_frames / 256)
+ * -- a frame's chunk number, then one uint32 per 256 frames.  Refused with
+ * LBF_ERR_INVALID before anything is enqueued: half of the flood table or of
+ * the dense tables, n_files > 0 with n_chunks == 0, n_frames or max_chunks
+ * over 2^31-1, with n_frames > 0 a NULL d_stream, d_frame_offsets,
+ * d_frame_lens, d_frames or d_work, a table that is not aligned to its element
+ * size or does not fit the allocation it points into (the names addressed
+ * through d_file_name_offsets are the caller's to place).  n_frames == 0
+ * returns LBF_OK and enqueues nothing, except that dense tables, when given,
+ * are made neutral and *d_n_located = 0. */
+#define LBF_FRAME_OTHER 0               /* not a well-formed SendChunk frame */
+#define LBF_FRAME_SEND_CHUNK 1          /* located and bound to a chunk of the flood table */
+#define LBF_FRAME_SEND_CHUNK_UNBOUND 2  /* located; file not in the table, index past the file's
+                                           chunks, or no table given */
+typedef struct lbf_wire_frame {   /* 32 bytes; offsets are positions in d_stream */
+  uint64_t text_offset;  /* first character behind <base64> */
+  uint64_t name_offset;  /* the file name as it stands in the frame (still XML-escaped) */
+  uint32_t text_len;     /* up to the next '<', exactly what DecodeSendChunk decodes */
+  uint32_t name_len;
+  uint32_t index;        /* bit for bit LocateSendChunk's o_index */
+  uint32_t kind;
+} lbf_wire_frame;
+
+uint64_t lbf_wire_frames_launch_work(uint64_t stream_len);
+int lbf_wire_frames_launch(const char* d_stream, uint64_t stream_len,
+                           uint64_t* d_frame_offsets, uint32_t* d_frame_lens, uint32_t max_frames,
+                           uint32_t* d_n_frames, uint64_t* d_tail, uint8_t* d_work, void* stream);
+
+uint64_t lbf_wire_send_chunks_launch_work(uint64_t n_frames);
+int lbf_wire_send_chunks_launch(const char* d_stream, uint64_t stream_len,
+        const uint64_t* d_frame_offsets, const uint32_t* d_frame_lens, uint32_t n_frames,
+        const uint32_t* d_n_frames /* NULL: n_frames is exact */,
+        /* flood table, all NULL / 0 together: */
+        const char* d_file_names, const uint32_t* d_file_name_offsets /* n_files + 1 */,
+        const uint32_t* d_file_first /* n_files + 1 */, uint32_t n_files,
+        const uint32_t* d_chunk_sizes, const uint8_t* d_chunk_expected, uint32_t n_chunks,
+        lbf_wire_frame* d_frames,
+        /* dense tables lbf_b64_verify_launch reads, all NULL / 0 together: */
+        uint64_t* d_text_offsets, uint32_t* d_text_lens, uint32_t* d_expected_sizes, uint8_t* d_expected,
+        uint32_t* d_chunk_of, uint32_t* d_frame_of, uint32_t max_chunks, uint32_t* d_n_located,
+        uint8_t* d_work, void* stream);
+
 /* Synthetic bytes (counter-mode splitmix64): fill
  * d_buf[0..len) with stream `seed` starting at stream byte `start`
  * (start % 8 == 0, d_buf 16-byte aligned). */
